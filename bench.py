@@ -8,7 +8,7 @@ One "step" = one pass of the WHOLE hot path over one batch, inputs already resid
   -> K x T reverse-diffusion steps (one hipGraph) -> convert_to_prob / mean / vote (-> RCCL all-gather for N>1).
 value = N * B*K*mc*T * steps / wall time (weak scaling: per-GPU batch fixed, no data-path collective).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 N > 1: either launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env), or
 invoked plainly -- the parent then starts the N ranks itself as child processes BEFORE it has touched the GPU, relays rank 0's
 line and exits non-zero if any rank did (launch_ranks below).
@@ -174,6 +174,23 @@ def shape_traffic(dtype: str, M: int, K: int):
                                                  "not measured by this run; FETCH_SIZE counts Infinity-Cache hits too")
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir: str, cap: int = DUMP_CAP_BYTES) -> None:
+    """--dump-outputs: each returned tensor as out_dir/<name>.npy, floating point as float32, integers as float64 (exact).  Should
+    the arrays exceed `cap` bytes together, each keeps its share of it as a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: (v.float() if v.is_floating_point() else v.double()).numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in arrs.items():
+        n = (a.nbytes * cap // total if total > cap else a.nbytes) // a.itemsize
+        if n < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def launch_ranks(n: int, argv) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as fresh child processes (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* in their environment, one GPU each), let rank 0 print the JSON line on the inherited stdout, and return non-zero
@@ -227,7 +244,12 @@ def main():
                          "never the headline (the reference computes in fp32)")
     ap.add_argument("--no-cpu-baseline", dest="cpu_baseline", action="store_false")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (samples, vote, prob, probs, yhat; prob_all for N > 1) as DIR/<name>.npy, "
+                         "rank 0 only: same arguments, same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -297,6 +319,8 @@ def main():
     for _ in range(args.warmup):
         step()
     dt, out = timed_steps(args.steps)
+    # out holds the library's fixed output buffers: copied to the host before the next step overwrites them
+    last_out = {k: v.detach().cpu().clone() for k, v in out.items()} if args.dump_outputs and rank == 0 else None
     head_us, pair_us, rec_us, n_probe = eng.profile_read()
     eng.set_profiling(False)
     chk = step()
@@ -440,6 +464,8 @@ def main():
                                             args.cpu_seconds)
     else:
         line["cpu_baseline"] = None
+    if last_out is not None:
+        dump_outputs(last_out, args.dump_outputs)
     print(json.dumps(line))
     if dist_on:
         torch.distributed.destroy_process_group()

@@ -19,8 +19,8 @@ Usage:  python tests/golden/gen_golden.py [--skip-full]            (re)write the
         python tests/golden/gen_golden.py --check [--skip-full]    regenerate into a temporary directory and compare with the COMMITTED
                                                                    files: same key sets, every array bit-identical (dtype, shape,
                                                                    bytes); exit status 1 and a list of differences otherwise.
-                                                                   tests/test_golden_fixtures.py runs this whenever /root/reference
-                                                                   is present, so a drifted or hand-edited fixture cannot go unnoticed.
+                                                                   Run it beside a reference checkout after touching a fixture: the
+                                                                   test suite cannot, since the reference is not part of the repository.
 """
 from __future__ import annotations
 

@@ -1,25 +1,15 @@
-"""The committed fixtures under tests/golden/ are exactly what the committed generator produces from the reference.
+"""The generator of the committed fixtures under tests/golden/.
 
-The reference ships no tests, so tests/golden/*.npz is the only pin of the oracle.  Whenever the reference checkout
-is present (the build container; never the GPU box) this re-runs tests/golden/gen_golden.py against it into a temporary directory
-and compares key sets and arrays bit for bit with the committed files (`--check`).  The two config-dim fixtures (2.6 GB of weights
-each) are left to `python tests/golden/gen_golden.py --check` without --skip-full."""
+The reference ships no tests, so tests/golden/*.npz is the only pin of the oracle.  The fixtures are produced by
+running the reference itself (tests/golden/gen_golden.py); that source is not part of this repository, so re-deriving them is a manual
+step beside a reference checkout: `python tests/golden/gen_golden.py --check` compares key sets and arrays bit for bit with the
+committed files.  These tests check that comparison itself and what every sampler fixture must carry."""
 import os
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEN = os.path.join(ROOT, "tests", "golden", "gen_golden.py")
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/diffusion"), reason="needs the reference checkout (build container only)")
-def test_committed_fixtures_are_what_the_generator_produces():
-    r = subprocess.run([sys.executable, GEN, "--check", "--skip-full"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "identical" in r.stdout and "DIFF" not in r.stdout
 
 
 def test_check_mode_notices_a_drifted_fixture(tmp_path):

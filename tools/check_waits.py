@@ -5,9 +5,10 @@ import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the k_skinny family is instantiated in csrc/nd_skinny_m{0,1,2}.hip (one translation unit per MODE): compiled side by side
 from concurrent.futures import ThreadPoolExecutor
+tmp = tempfile.TemporaryDirectory(prefix="nd_check_waits_")      # private: a shared temp dir may hold another user's files of the same name
 def isa(m):
     src = os.path.join(root, "nested_diffusion_amd", "csrc", f"nd_skinny_m{m}.hip")
-    out = os.path.join(tempfile.gettempdir(), f"nd_skinny_m{m}_check.s")
+    out = os.path.join(tmp.name, f"nd_skinny_m{m}_check.s")
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", src, "-S", "--cuda-device-only", "-o", out],
                    check=True, stderr=subprocess.DEVNULL)
     return open(out).read()
