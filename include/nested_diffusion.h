@@ -401,6 +401,45 @@ int nd_sample_stats(const float *probs_dev, float *piw_out_dev, float *var_out_d
 int nd_report(const float *piw_dev, const float *var_dev, const float *prob_mean_dev, const int64_t *vote_dev,
               const int64_t *target_dev, float *out_dev, int N, int C, float temperature, int n_bins, void *stream);
 
+/* ---- input gradient of the full ViT and the Linf attacks (the reference attacks cond_pred_model['vit'] with foolbox 3.x:
+ * attack.py, classification_train_separately.py:661-667, utils.py:258-269).  All fp32; only the input gradient is formed.
+ * The Linear layers' input gradients are nd_gemm_split calls with the frag32b3 image of W^T as the weight operand.
+ *   nd_layernorm_bwd      LayerNorm input gradient: out = rstd * (gg - mean(gg) - xh * mean(gg * xh)) (+ residual), gg = g * gamma,
+ *                         xh = (x - mean) * rstd, mean / rstd recomputed from x as nd_layernorm does; out fp32 [rows, dim] and / or
+ *                         out_split its frag32b3 image (dim % 32 == 0); either may be NULL, not both.  dim % 4 == 0, dim <= 2048.
+ *   nd_gelu_split         GELU (exact erf, the fc1 epilogue's expression) of u [rows, cols]: the frag32b3 image (and optionally fp32
+ *                         out) -- the fc2 operand when fc1 runs without its activation so that u is kept.  cols % 32 == 0.
+ *   nd_gelu_bwd_split     dg * gelu'(u) as the frag32b3 image (and optionally fp32 out).
+ *   nd_attention_bwd      qkv fp32 [B*N, 3*heads*64] (timm layout), o = the forward output [B*N, heads*64], dout its gradient ->
+ *                         dqkv fp32 [B*N, 3*heads*64] and / or its frag32b3 image.  P is recomputed from q, k; one workgroup per
+ *                         (image, head), no atomics (bitwise reproducible).  1 <= N <= 208, d = 64.
+ *   nd_xent_head_bwd      d = softmax(logits) - onehot(label) (gradient of the summed cross-entropy), dfeat [B, E] = d . head_w
+ *                         ([C, E]); loss [B] (may be NULL) = logsumexp(logits) - logits[label].  C <= 1024.
+ *   nd_unpatchify         the exact inverse permutation of nd_patchify: cols [B*(H/p)*(W/p), Cin*p*p] -> img [B, Cin, H, W].
+ *   nd_linf_step          out = clip(x0 + clip(x + alpha * sign(grad) - x0, -eps, eps), lo, hi), sign(0) = 0, each operation one
+ *                         rounded fp32 op in this order (foolbox: step, project, clip to the bounds).  grad NULL: no step (with
+ *                         lo = -inf, hi = inf this is foolbox's final clip_perturbation).  n elements.
+ *   nd_linf_random_start  out = clip(x0 + eps * w, lo, hi) for B images of per_image elements (per_image % 4 == 0).  Element 4q + e of
+ *                         image b draws word e of Philox4x32-10 (nd_rng) with key = (seed low word, seed high word) and
+ *                         counter = (first_image + b, q, restart, ND_LINF_START_TAG); the word x becomes
+ *                         u = float(x >> 8) * 2^-24 (exact, [0, 1)), w = 2u - 1 (exact, [-1, 1)), then eps * w and x0 + that are
+ *                         single fp32 roundings.  first_image = the global index of the first image (its index in the dataset or
+ *                         test stream): an image draws the same start at any batch size and on any rank. */
+#define ND_LINF_START_TAG 0x41544B31u
+int nd_layernorm_bwd(const float *x_dev, const float *gamma_dev, const float *g_dev, const float *residual_dev, float *out_dev,
+                     void *out_split_dev, int rows, int dim, float eps, void *stream);
+int nd_gelu_split(const float *u_dev, float *out_dev, void *out_split_dev, int rows, int cols, void *stream);
+int nd_gelu_bwd_split(const float *u_dev, const float *dg_dev, float *out_dev, void *out_split_dev, int rows, int cols, void *stream);
+int nd_attention_bwd(const float *qkv_dev, const float *o_dev, const float *dout_dev, float *dqkv_dev, void *dqkv_split_dev,
+                     int B, int N, int heads, void *stream);
+int nd_xent_head_bwd(const float *logits_dev, const int64_t *labels_dev, const float *head_w_dev, float *dfeat_dev, float *loss_dev,
+                     int B, int C, int E, void *stream);
+int nd_unpatchify(const float *cols_dev, float *img_dev, int B, int Cin, int Himg, int Wimg, int p, void *stream);
+int nd_linf_step(const float *x_dev, const float *x0_dev, const float *grad_dev, float *out_dev, size_t n, float alpha, float eps,
+                 float lo, float hi, void *stream);
+int nd_linf_random_start(const float *x0_dev, float *out_dev, int B, size_t per_image, uint64_t seed, uint32_t first_image,
+                         uint32_t restart, float eps, float lo, float hi, void *stream);
+
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */
 /* add_noise (:272-279): out = x + z * std, z = the randn_like draw (supplied, like the sampler's noise). */

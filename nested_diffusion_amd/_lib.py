@@ -157,6 +157,14 @@ SIGNATURES = {
     "nd_img_contrast": (_i, [_vp, _vp, _vp, _i, _sz, _f, _vp]),
     "nd_img_resize_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "nd_img_cover": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "nd_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "nd_gelu_split": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "nd_gelu_bwd_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "nd_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_xent_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_unpatchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "nd_linf_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _vp]),
+    "nd_linf_random_start": (_i, [_vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, C.c_uint32, _f, _f, _f, _vp]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
 }
 

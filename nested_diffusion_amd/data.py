@@ -57,15 +57,16 @@ class ImageFolderDataset(torch.utils.data.Dataset):
     loader) followed by the reference's test-time transforms (dataset_helper/chest_x_ray_dataset.py:31-51, 76-96):
       grayscaled:   Grayscale(num_output_channels=3) -> Resize((224, 224)) -> ToTensor
       standardized: Resize((224, 224)) -> ToTensor -> Normalize(pre-calculated mean, std)
+      attacked:     Resize((224, 224)) -> ToTensor (data_loader_attacks, :197-227: the adversarial PNG trees, already in [0, 1] RGB)
     written with the PIL calls torchvision makes for PIL inputs (L conversion, BILINEAR resize, /255)."""
 
     def __init__(self, root: str, dataset_name: str, preprocess: str, image_size=(224, 224)):
         from PIL import Image  # noqa: F401  (fail early if absent)
         if not os.path.isdir(root):
             raise FileNotFoundError(f"dataset directory not found: {root}")
-        if preprocess not in ("grayscaled", "standardized"):
+        if preprocess not in ("grayscaled", "standardized", "attacked"):
             raise ValueError("Invalid preprocess type")
-        if dataset_name not in PRECAL:
+        if preprocess != "attacked" and dataset_name not in PRECAL:
             raise ValueError("Dataset name is not valid")
         self.classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
         if not self.classes:
@@ -78,7 +79,8 @@ class ImageFolderDataset(torch.utils.data.Dataset):
                     if f.lower().endswith(IMG_EXTENSIONS):
                         self.samples.append((os.path.join(d, f), self.class_to_idx[c]))
         self.preprocess, self.size = preprocess, tuple(image_size)
-        self.mean, self.std = (torch.tensor(v).view(3, 1, 1) for v in PRECAL[dataset_name])
+        if preprocess != "attacked":
+            self.mean, self.std = (torch.tensor(v).view(3, 1, 1) for v in PRECAL[dataset_name])
 
     def __len__(self):
         return len(self.samples)
@@ -99,10 +101,18 @@ class ImageFolderDataset(torch.utils.data.Dataset):
         return x, target
 
 
+ATTACKS = ("FGSM", "PGD", "BIM", "AUTOPGD", "CW")
+ATTACKED_DATASETS = tuple(f"{d}Atk{a}" for d in ("ChestXRay", "ISICSkinCancer") for a in ATTACKS)   # diffusion/utils.py:165-177
+
+
 def get_dataset(args, config):
-    """The ChestXRay / ISICSkinCancer (+ *Validate) branches of diffusion/utils.py:146-164: returns the split the
-    test / calibration loop iterates (testing, or validation for the *Validate names)."""
+    """The ChestXRay / ISICSkinCancer (+ *Validate, *Atk*) branches of diffusion/utils.py:146-177: returns the split the
+    test / calibration loop iterates (testing, or validation for the *Validate names; for the attacked names the
+    <dataroot>/Test_attacks_<NAME> tree that make_attacks writes, read as data_loader_attacks reads it)."""
     name = config.data.dataset
+    if name in ATTACKED_DATASETS:
+        attack = name.split("Atk", 1)[1]
+        return ImageFolderDataset(os.path.join(config.data.dataroot, f"Test_attacks_{attack}"), name.split("Atk", 1)[0], "attacked")
     base = {"ChestXRay": "ChestXRay", "ISICSkinCancer": "ISICSkinCancer", "ChestXRayValidate": "ChestXRay",
             "ISICSkinCancerValidate": "ISICSkinCancer"}.get(name)
     if base is None:

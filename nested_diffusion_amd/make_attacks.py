@@ -1,0 +1,79 @@
+"""Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
+
+    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD --eps E --out ROOT \
+        [--preprocess grayscaled] [--seed S] [--batch_size B]
+
+Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
+test split (the PGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
+as RGB uint8 = round(255 * adv), with the classes and file stems of the source: the tree data_loader_attacks reads
+(dataset_helper/chest_x_ray_dataset.py:197-227; here data.get_dataset with a *Atk<NAME> dataset name).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="write an attacked test set (Test_attacks_<NAME>) with the GPU attacks of attack.py")
+    p.add_argument("--config", type=str, required=True)
+    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD"], required=True)
+    p.add_argument("--eps", type=float, required=True)
+    p.add_argument("--out", type=str, required=True, help="root the Test_attacks_<NAME> tree is written under")
+    p.add_argument("--preprocess", type=str, choices=["grayscaled", "standardized"], default="grayscaled")
+    p.add_argument("--seed", type=int, default=0, help="key of the PGD random start")
+    p.add_argument("--batch_size", type=int, default=32)
+    p.add_argument("--dataroot", type=str, default=None)
+    p.add_argument("--device", type=int, default=0)
+    return p
+
+
+def main(argv=None) -> int:
+    from PIL import Image
+
+    from . import main as nd_main
+    from .attack import Attack
+    from .data import get_dataset
+    from .mapping import VisionTransformer, load_pickled
+    from .runner import CHEST
+
+    args = build_parser().parse_args(argv)
+    with open(args.config) as f:
+        import yaml
+        config = nd_main.dict2namespace(yaml.safe_load(f))
+    if args.dataroot is not None:
+        config.data.dataroot = args.dataroot
+    base = config.data.dataset.split("Atk", 1)[0].replace("Validate", "")
+    config.data.dataset = base                          # the clean test split of the config's dataset
+    ds = get_dataset(args, config)
+    device = torch.device("cuda", args.device)
+    ckpt = "ChestXRay" if base in CHEST else "ISICSkinCancer"
+    sd = load_pickled(os.path.join(config.diffusion.trained_aux_cls_ckpt_path, f"vit_base_patch16_224_{ckpt}.pth"))
+    vit = VisionTransformer(sd, max(1, sd["patch_embed.proj.weight"].shape[0] // 64), device)
+    attack = Attack(args.eps, args.attack_name, vit, seed=args.seed)
+    out_root = os.path.join(args.out, f"Test_attacks_{args.attack_name}")
+    n_ok = 0
+    for start in range(0, len(ds), args.batch_size):
+        idx = list(range(start, min(start + args.batch_size, len(ds))))
+        items = [ds[i] for i in idx]
+        x = torch.stack([it[0] for it in items]).to(device)
+        y = torch.tensor([it[1] for it in items], dtype=torch.int64, device=device)
+        adv, success = attack.generate_attack(x, y, first_image=start)
+        n_ok += int(success.sum())
+        pix = torch.round(adv.clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+        for k, i in enumerate(idx):
+            path, target = ds.samples[i]
+            d = os.path.join(out_root, ds.classes[target])
+            os.makedirs(d, exist_ok=True)
+            stem = os.path.splitext(os.path.basename(path))[0]
+            Image.fromarray(np.ascontiguousarray(pix[k]), "RGB").save(os.path.join(d, stem + ".png"))
+    print(f"{args.attack_name} eps={args.eps}: {len(ds)} images written under {out_root}, {n_ok} successful attacks")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

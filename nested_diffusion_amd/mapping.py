@@ -97,31 +97,44 @@ class VisionTransformer:
         cols = ops.patchify(x, self.patch)
         return ops.gemm_bias_act(cols, self.pe_w, self.p["patch_embed.proj.bias"])
 
-    def block(self, i: int, tok: torch.Tensor, B: int) -> torch.Tensor:
-        """Block.forward on tokens [B*N, embed]."""
+    def block(self, i: int, tok: torch.Tensor, B: int, rec: Optional[dict] = None) -> torch.Tensor:
+        """Block.forward on tokens [B*N, embed].  rec (input_grad): a dict that receives what the backward needs -- the block input x,
+        the fp32 qkv, the attention output o, the mid-block tokens x2 and the fc1 pre-activation u.  fc1 then runs without its
+        activation and the GELU follows as its own kernel (the epilogue's expression, written as the fc2 operand image): same values."""
         p, pre = self.p, f"blocks.{i}."
         N = tok.shape[0] // B
+        x = tok
         h = ops.layernorm(tok, p[pre + "norm1.weight"], p[pre + "norm1.bias"], LN_EPS)
         if self.split and ops.qkv_images_supported(N, self.num_heads) and not os.environ.get("ND_ATT_F32"):
             # attention on the bf16 matrix pipe as well: the qkv Linear writes the attention kernel's operand images (nd_vit_block's sequence)
             img = ops.gemm_split_qkv(ops.split_rows(h), p[pre + "attn.qkv.weight"], p[pre + "attn.qkv.bias"], B, N, self.num_heads)
             a = ops.attention_images(img, B, N, self.num_heads)
+            qkv = ops.gemm_bias_act(h, p[pre + "attn.qkv.weight"], p[pre + "attn.qkv.bias"]) if rec is not None else None
         else:
             qkv = ops.gemm_bias_act(h, p[pre + "attn.qkv.weight"], p[pre + "attn.qkv.bias"])
             a = ops.attention(qkv, B, N, self.num_heads, self.dtype)
         tok = ops.gemm_bias_act(a, p[pre + "attn.proj.weight"], p[pre + "attn.proj.bias"], residual=tok)
         h = ops.layernorm(tok, p[pre + "norm2.weight"], p[pre + "norm2.bias"], LN_EPS)
-        h = ops.gemm_bias_act(h, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], act="gelu")
-        return ops.gemm_bias_act(h, p[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"], residual=tok)
+        if rec is None:
+            h = ops.gemm_bias_act(h, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"], act="gelu")
+            return ops.gemm_bias_act(h, p[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"], residual=tok)
+        u = ops.gemm_bias_act(h, p[pre + "mlp.fc1.weight"], p[pre + "mlp.fc1.bias"])
+        rec.update(x=x, qkv=qkv, o=a, x2=tok, u=u)
+        return ops.gemm_split(ops.gelu_split(u), p[pre + "mlp.fc2.weight"], p[pre + "mlp.fc2.bias"], residual=tok)
+
+    def _tokens(self, x: torch.Tensor) -> torch.Tensor:
+        """patch_embed + cls token + pos_embed -> [B*N, embed]"""
+        B = x.shape[0]
+        tok = self.patch_embed(x).reshape(B, -1, self.embed_dim)
+        tok = torch.cat((self.p["cls_token"].expand(B, -1, -1), tok), dim=1) + self.p["pos_embed"]
+        return tok.reshape(-1, self.embed_dim).contiguous()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Full VisionTransformer.forward (cls token + pos_embed, all blocks, norm, head on cls).
         Only feeds the never-sampled last element of compute_guiding_prediction."""
         B = x.shape[0]
-        tok = self.patch_embed(x).reshape(B, -1, self.embed_dim)
-        tok = torch.cat((self.p["cls_token"].expand(B, -1, -1), tok), dim=1) + self.p["pos_embed"]
-        N = tok.shape[1]
-        tok = tok.reshape(B * N, self.embed_dim).contiguous()
+        tok = self._tokens(x)
+        N = tok.shape[0] // B
         for i in range(self.depth):
             tok = self.block(i, tok, B)
         cls = tok.reshape(B, N, self.embed_dim)[:, 0].contiguous()
@@ -129,6 +142,61 @@ class VisionTransformer:
         return ops.linear(cls, self.p["head.weight"], self.p["head.bias"])
 
     __call__ = forward
+
+    # ---- input gradient (the Linf attacks of attack.py) ------------------------------------------------------------------------
+    def transposed_weights(self) -> Dict[str, "ops.SplitMatrix"]:
+        """frag32b3 images of W^T for every Linear layer and the patch embedding: the weight operands of the input-gradient GEMMs
+        (dX = dY . W).  Built once, on the first gradient request (~0.5 GB for ViT-B/16); a ViT that is never attacked never holds them."""
+        if getattr(self, "_wT", None) is None:
+            if not self.split:
+                raise _lib.NdError("input_grad runs in the default fp32 (split) form only: not in fp16 mode or with ND_GEMM_F32=mfma_f32")
+            wT = {}
+            for k, w in list(self.p.items()) + [("patch_embed", self.pe_w)]:
+                if isinstance(w, ops.SplitMatrix):
+                    wT[k] = ops.split_rows(ops.join_rows(w).t().contiguous())
+            self._wT = wT
+        return self._wT
+
+    def _block_grad(self, i: int, r: dict, dy: torch.Tensor, dy_img: "ops.SplitMatrix", B: int):
+        """dL/d(block input) from dy = dL/d(block output): fp32 and its frag32b3 image."""
+        wT, p, pre = self._wT, self.p, f"blocks.{i}."
+        N = dy.shape[0] // B
+        dg = ops.gemm_split(dy_img, wT[pre + "mlp.fc2.weight"])
+        dh = ops.gemm_split(ops.gelu_grad_split(r["u"], dg), wT[pre + "mlp.fc1.weight"])
+        dx2, dx2_img = ops.layernorm_grad(r["x2"], p[pre + "norm2.weight"], dh, LN_EPS, residual=dy, want_split=True)
+        da = ops.gemm_split(dx2_img, wT[pre + "attn.proj.weight"])
+        dqkv = ops.attention_grad(r["qkv"], r["o"], da, B, N, self.num_heads, want_out=False, want_split=True)
+        dh = ops.gemm_split(dqkv, wT[pre + "attn.qkv.weight"])
+        return ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh, LN_EPS, residual=dx2, want_split=True)
+
+    def input_grad(self, x: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(logits, dx, loss): the forward (the same kernels in the same order as forward(): its logits equal forward(x) bit for bit),
+        then the gradient of crossentropy(logits, labels).sum() -- foolbox's loss -- with respect to the input image x [B, 3, H, W],
+        and the per-image cross-entropy."""
+        x = ops._f32(x, "x")
+        wT = self.transposed_weights()
+        B, _, H, W = x.shape
+        tok = self._tokens(x)
+        N = tok.shape[0] // B
+        recs = []
+        for i in range(self.depth):
+            recs.append({})
+            tok = self.block(i, tok, B, rec=recs[-1])
+        cls_in = tok.reshape(B, N, self.embed_dim)[:, 0].contiguous()
+        cls = ops.layernorm(cls_in, self.p["norm.weight"], self.p["norm.bias"], LN_EPS)
+        logits = ops.linear(cls, self.p["head.weight"], self.p["head.bias"])
+        dcls, loss = ops.xent_head_grad(logits, labels, self.p["head.weight"])
+        dcls = ops.layernorm_grad(cls_in, self.p["norm.weight"], dcls, LN_EPS)
+        dy = torch.zeros(B, N, self.embed_dim, dtype=torch.float32, device=x.device)
+        dy[:, 0] = dcls                                       # only the cls token reaches the head
+        dy = dy.reshape(B * N, self.embed_dim)
+        dy_img = ops.split_rows(dy)
+        for i in reversed(range(self.depth)):
+            dy, dy_img = self._block_grad(i, recs[i], dy, dy_img, B)
+            recs[i] = None
+        dpatch = dy.reshape(B, N, self.embed_dim)[:, 1:].reshape(-1, self.embed_dim).contiguous()   # cls token / pos_embed: no input path
+        dcols = ops.gemm_split(dpatch, wT["patch_embed"])
+        return logits, ops.unpatchify(dcols, B, self.in_chans, H, W, self.patch), loss
 
 
 class GuidingConditioner:

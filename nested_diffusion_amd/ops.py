@@ -325,3 +325,130 @@ def report(piw: torch.Tensor, var: torch.Tensor, prob_mean: torch.Tensor, vote: 
     o = out.cpu()
     return {"accuracy": o[0], "ece": o[1], "piw_correct": o[2:2 + C], "piw_incorrect": o[2 + C:2 + 2 * C],
             "var_correct": o[2 + 2 * C:2 + 3 * C], "var_incorrect": o[2 + 3 * C:2 + 4 * C]}
+
+
+# ---- input gradient of the ViT and the Linf attack steps (csrc/nd_vit_grad.hip) ------------------------------------------------
+def _image_or_tensor(out: torch.Tensor, osp: Optional[SplitMatrix], want_out: bool, want_split: bool):
+    if want_out and want_split:
+        return out, osp
+    return osp if want_split else out
+
+
+def layernorm_grad(x: torch.Tensor, weight: torch.Tensor, g: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
+                   want_out: bool = True, want_split: bool = False):
+    """Input gradient of LayerNorm(x) * weight + bias given g = dL/d(output), plus `residual` (the gradient the residual stream carries
+    past the LayerNorm).  mean / rstd are recomputed from x.  Returns fp32 [rows, dim], its frag32b3 image (want_split), or both."""
+    x, g = _f32(x, "x"), _f32(g, "g")
+    if g.shape != x.shape:
+        raise ValueError(f"g is {tuple(g.shape)}, x is {tuple(x.shape)}")
+    residual = _f32(residual, "residual") if residual is not None else None
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("residual must have the shape of x")
+    if not (want_out or want_split):
+        raise ValueError("nothing to return")
+    dim = x.shape[-1]
+    rows = x.numel() // dim
+    out = torch.empty_like(x) if want_out else None
+    osp = SplitMatrix(rows, dim, x.device) if want_split else None
+    check(_lib.load().nd_layernorm_bwd(ptr(x), ptr(_f32(weight, "weight")), ptr(g), ptr(residual), ptr(out), ptr(osp.data) if osp else None,
+                                       rows, dim, float(eps), _stream(x)), "nd_layernorm_bwd")
+    return _image_or_tensor(out, osp, want_out, want_split)
+
+
+def gelu_split(u: torch.Tensor, want_out: bool = False):
+    """GELU(u) (exact erf, the expression of the fc1 epilogue) written as the frag32b3 image of [rows, cols] (and fp32 with want_out)."""
+    u = _f32(u, "u")
+    rows, cols = u.shape
+    out = torch.empty_like(u) if want_out else None
+    osp = SplitMatrix(rows, cols, u.device)
+    check(_lib.load().nd_gelu_split(ptr(u), ptr(out), ptr(osp.data), rows, cols, _stream(u)), "nd_gelu_split")
+    return _image_or_tensor(out, osp, want_out, True)
+
+
+def gelu_grad_split(u: torch.Tensor, dg: torch.Tensor, want_out: bool = False):
+    """dg * GELU'(u) as the frag32b3 image of [rows, cols] (and fp32 with want_out)."""
+    u, dg = _f32(u, "u"), _f32(dg, "dg")
+    if dg.shape != u.shape:
+        raise ValueError(f"dg is {tuple(dg.shape)}, u is {tuple(u.shape)}")
+    rows, cols = u.shape
+    out = torch.empty_like(u) if want_out else None
+    osp = SplitMatrix(rows, cols, u.device)
+    check(_lib.load().nd_gelu_bwd_split(ptr(u), ptr(dg), ptr(out), ptr(osp.data), rows, cols, _stream(u)), "nd_gelu_bwd_split")
+    return _image_or_tensor(out, osp, want_out, True)
+
+
+def attention_grad(qkv: torch.Tensor, o: torch.Tensor, dout: torch.Tensor, B: int, N: int, heads: int, want_out: bool = True,
+                   want_split: bool = False):
+    """dqkv [B*N, 3*heads*64] of o = softmax(q k^T / 8) v (timm layout) given dout = dL/do; fp32, its frag32b3 image, or both."""
+    qkv, o, dout = _f32(qkv, "qkv"), _f32(o, "o"), _f32(dout, "dout")
+    if tuple(qkv.shape) != (B * N, 3 * heads * 64) or tuple(o.shape) != (B * N, heads * 64) or dout.shape != o.shape:
+        raise ValueError(f"qkv {tuple(qkv.shape)}, o {tuple(o.shape)}, dout {tuple(dout.shape)} do not match B={B}, N={N}, heads={heads}")
+    if not (want_out or want_split):
+        raise ValueError("nothing to return")
+    out = torch.empty_like(qkv) if want_out else None
+    osp = SplitMatrix(B * N, 3 * heads * 64, qkv.device) if want_split else None
+    check(_lib.load().nd_attention_bwd(ptr(qkv), ptr(o), ptr(dout), ptr(out), ptr(osp.data) if osp else None, B, N, heads, _stream(qkv)),
+          "nd_attention_bwd")
+    return _image_or_tensor(out, osp, want_out, want_split)
+
+
+def xent_head_grad(logits: torch.Tensor, labels: torch.Tensor, head_w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dfeat [B, E] = (softmax(logits) - onehot(labels)) . head_w, per-image cross-entropy [B]): the gradient of
+    crossentropy(logits, labels).sum() with respect to the head's input."""
+    logits, head_w = _f32(logits, "logits"), _f32(head_w, "head_w")
+    B, C = logits.shape
+    if head_w.dim() != 2 or head_w.shape[0] != C:
+        raise ValueError(f"head_w is {tuple(head_w.shape)}, logits {tuple(logits.shape)}")
+    labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+    if labels.shape != (B,):
+        raise ValueError(f"labels must be [{B}]")
+    if B and (int(labels.min()) < 0 or int(labels.max()) >= C):
+        raise ValueError(f"labels must lie in [0, {C})")
+    E = head_w.shape[1]
+    dfeat = torch.empty(B, E, dtype=torch.float32, device=logits.device)
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(_lib.load().nd_xent_head_bwd(ptr(logits), ptr(labels), ptr(head_w), ptr(dfeat), ptr(loss), B, C, E, _stream(logits)),
+          "nd_xent_head_bwd")
+    return dfeat, loss
+
+
+def unpatchify(cols: torch.Tensor, B: int, Cin: int, H: int, W: int, p: int) -> torch.Tensor:
+    """[B*(H/p)*(W/p), Cin*p*p] -> [B, Cin, H, W]: the exact inverse of patchify."""
+    cols = _f32(cols, "cols")
+    if H % p or W % p or tuple(cols.shape) != (B * (H // p) * (W // p), Cin * p * p):
+        raise ValueError(f"cols is {tuple(cols.shape)}; expected [{B * (H // p) * (W // p)}, {Cin * p * p}]")
+    img = torch.empty(B, Cin, H, W, dtype=torch.float32, device=cols.device)
+    check(_lib.load().nd_unpatchify(ptr(cols), ptr(img), B, Cin, H, W, p, _stream(cols)), "nd_unpatchify")
+    return img
+
+
+def linf_step(x: torch.Tensor, x0: torch.Tensor, grad: Optional[torch.Tensor], alpha: float, eps: float, lo: float = 0.0,
+              hi: float = 1.0) -> torch.Tensor:
+    """clip(x0 + clip(x + alpha * sign(grad) - x0, -eps, eps), lo, hi) (foolbox's step, project, clip).  grad None: no step --
+    with lo = -inf, hi = inf that is foolbox's final clip_perturbation."""
+    x, x0 = _f32(x, "x"), _f32(x0, "x0")
+    if x0.shape != x.shape:
+        raise ValueError("x0 must have the shape of x")
+    if grad is not None:
+        grad = _f32(grad, "grad")
+        if grad.shape != x.shape:
+            raise ValueError("grad must have the shape of x")
+    out = torch.empty_like(x)
+    check(_lib.load().nd_linf_step(ptr(x), ptr(x0), ptr(grad), ptr(out), x.numel(), float(alpha), float(eps), float(lo), float(hi),
+                                   _stream(x)), "nd_linf_step")
+    return out
+
+
+def linf_random_start(x0: torch.Tensor, eps: float, seed: int, first_image: int = 0, restart: int = 0, lo: float = 0.0,
+                      hi: float = 1.0) -> torch.Tensor:
+    """clip(x0 + U[-eps, eps), lo, hi) per image; the draws of image b are keyed on (seed, first_image + b, element, restart), so an
+    image draws the same start at any batch size (include/nested_diffusion.h: nd_linf_random_start)."""
+    x0 = _f32(x0, "x0")
+    B = x0.shape[0]
+    per = x0.numel() // max(B, 1)
+    if per % 4:
+        raise ValueError("the elements per image must be a multiple of 4")
+    out = torch.empty_like(x0)
+    check(_lib.load().nd_linf_random_start(ptr(x0), ptr(out), B, per, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image) & 0xFFFFFFFF,
+                                           int(restart) & 0xFFFFFFFF, float(eps), float(lo), float(hi), _stream(x0)), "nd_linf_random_start")
+    return out

@@ -249,7 +249,8 @@ class Diffusion(object):
         if first is None:
             return
         x0, _ = rows_of(first)
-        direct = (not x0.is_cuda) and not self._perturbs() and self.engine is not None and x0.dim() == 4
+        direct = (not x0.is_cuda) and not self._perturbs() and self.engine is not None and x0.dim() == 4 \
+            and getattr(self, "_attack", None) is None                      # an attack reads the batch while the next one uploads
         if direct:
             eng = self.engine
             eng.enable_input_flag()
@@ -373,9 +374,10 @@ class Diffusion(object):
         return images_224
 
     # ---- test loop ----------------------------------------------------------------------------
-    def test_atk(self, test_loader=None):
+    def test_atk(self, test_loader=None, attack=None):
         """:631-840: input perturbations (:726-737), the hot path, and the report the reference prints (accuracy, ECE,
-        per-class PIW and variances, :801-838).  Adversarial attacks (:738-739) need ViT gradients and raise."""
+        per-class PIW and variances, :801-838).  attack: an attack.Attack applied to this rank's rows after the perturbations
+        (:738-739; the random start of image i is keyed on its global index).  The --attack_name switch itself still raises."""
         args, config = self.args, self.config
         if getattr(args, "attack_name", None) not in (None, "None"):
             raise NotImplementedError("adversarial attacks need gradients through the ViT: out of scope")
@@ -391,7 +393,11 @@ class Diffusion(object):
         self._seed_noise(lo)
         mv_class, target_class, prob_mc, piw_mc, var_mc = [], [], [], [], []
         n_step_img, t0 = 0, time.time()
-        for images, target in self._rank_batches(test_loader, lo, hi, B):   # :715-737, this rank's rows only
+        self._attack = attack
+        for n_batch, (images, target) in enumerate(self._rank_batches(test_loader, lo, hi, B)):   # :715-737, this rank's rows only
+            if attack is not None:                                           # :738-739
+                from .attack import apply_attack
+                images = apply_attack(attack, images, target, attack.attack_type, first_image=n_batch * B + lo)
             out = self.predict_batch(images, clone=False)
             # spread of the K*mc per-sample probabilities per image (what the reference keeps in pred_mc, quirk Q4)
             piw, var = ops.sample_stats(out["probs"])

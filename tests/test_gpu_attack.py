@@ -1,0 +1,248 @@
+"""Input gradient of the full ViT on the GPU (csrc/nd_vit_grad.hip, VisionTransformer.input_grad) and the Linf attacks built on it
+(nested_diffusion_amd/attack.py), against torch.autograd through the CPU oracle in float64."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import ref_cpu
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+TAU = 1e-3
+LN_EPS = 1e-6
+
+
+def rel_l2(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return float((a - b).norm() / b.norm())
+
+
+def f64(vp):
+    return {k: v.double() for k, v in vp.items()}
+
+
+def ref_grad(vp64, x, labels, heads, depth):
+    """(logits, d/dx crossentropy(logits, labels).sum()) through the oracle in float64."""
+    xx = x.double().cpu().clone().requires_grad_(True)
+    logits = ref_cpu.vit_full_forward(vp64, xx, heads, depth)
+    F.cross_entropy(logits, labels.cpu(), reduction="sum").backward()
+    return logits.detach(), xx.grad
+
+
+def oracle_step(x, x0, g, alpha, eps, lo=0.0, hi=1.0):
+    """foolbox's step / project / clip in float32 on the host, each operation one rounding."""
+    a, e = float(np.float32(alpha)), float(np.float32(eps))
+    x, x0 = x.float().cpu(), x0.float().cpu()
+    t = x + a * torch.sign(g.cpu()).float()
+    d = torch.clamp(t - x0, -e, e)
+    return torch.clamp(x0 + d, lo, hi)
+
+
+def oracle_random_start(x0, eps, seed, first_image, restart=0):
+    x0 = x0.float().cpu()
+    B = x0.shape[0]
+    per = x0[0].numel()
+    Q = per // 4
+    b, q = np.meshgrid(np.arange(B), np.arange(Q), indexing="ij")
+    ctr = np.stack([(first_image + b) & 0xFFFFFFFF, q, np.full_like(q, restart), np.full_like(q, 0x41544B31)], axis=-1).reshape(-1, 4)
+    w = ref_cpu.philox4x32_10(ctr, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF).reshape(B, per)
+    u = (w >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    s = np.float32(2.0) * u - np.float32(1.0)
+    y = x0.numpy().reshape(B, per) + np.float32(eps) * s
+    return torch.from_numpy(np.clip(y, np.float32(0.0), np.float32(1.0)).reshape(x0.shape))
+
+
+def agree_except_near_zero(a, b, g_ref):
+    """a == b bitwise wherever |g_ref| > TAU * max|g_ref| (a near-zero gradient may take either sign under fp32 rounding)."""
+    g = g_ref.cpu().double()
+    mask = g.abs() > TAU * g.abs().max()
+    return bool(torch.equal(a.cpu()[mask], b.cpu()[mask])), float(mask.double().mean())
+
+
+# ---- models -------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def tiny():
+    from nested_diffusion_amd.mapping import VisionTransformer
+    vp = ref_cpu.init_vit_params(embed=128, depth=5, patch=16, img=32, seed=3)
+    return VisionTransformer(vp, 2, DEV), vp, 2, 5, 32
+
+
+@pytest.fixture(scope="module")
+def vitb():
+    from nested_diffusion_amd.mapping import VisionTransformer
+    vp = ref_cpu.init_vit_params(embed=768, depth=12, patch=16, img=224, seed=11)
+    return VisionTransformer(vp, 12, DEV), vp, 12, 12, 224
+
+
+def images(B, img, seed):
+    return torch.rand(B, 3, img, img, generator=torch.Generator().manual_seed(seed))
+
+
+# ---- 1. primitives --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("rows", [6304, 32])
+def test_layernorm_grad(rows):
+    from nested_diffusion_amd import ops
+    g = torch.Generator().manual_seed(rows)
+    x = torch.randn(rows, 768, generator=g) * 2 + 0.3
+    w = 1 + 0.1 * torch.randn(768, generator=g)
+    dy = torch.randn(rows, 768, generator=g)
+    res = torch.randn(rows, 768, generator=g)
+    xx = x.double().requires_grad_(True)
+    F.layer_norm(xx, (768,), w.double(), torch.zeros(768, dtype=torch.float64), LN_EPS).backward(dy.double())
+    out, img = ops.layernorm_grad(x.to(DEV), w.to(DEV), dy.to(DEV), LN_EPS, residual=res.to(DEV), want_split=True)
+    assert rel_l2(out.cpu() - res, xx.grad) <= 1e-5
+    assert torch.equal(ops.join_rows(img), out)
+    plain = ops.layernorm_grad(x.to(DEV), w.to(DEV), dy.to(DEV), LN_EPS)
+    assert rel_l2(plain, xx.grad) <= 1e-5
+
+
+def _attn_ref(qkv, B, N, heads):
+    q, k, v = qkv.reshape(B, N, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    a = ((q @ k.transpose(-2, -1)) * 0.125).softmax(-1)
+    return (a @ v).transpose(1, 2).reshape(B * N, heads * 64)
+
+
+@pytest.mark.parametrize("N", [197, 196, 50, 5])
+@pytest.mark.parametrize("heads", [12, 2])
+def test_attention_grad(N, heads):
+    from nested_diffusion_amd import ops
+    B = 2
+    g = torch.Generator().manual_seed(N * 100 + heads)
+    qkv = torch.randn(B * N, 3 * heads * 64, generator=g)
+    dout = torch.randn(B * N, heads * 64, generator=g)
+    o = ops.attention(qkv.to(DEV), B, N, heads)
+    qq = qkv.double().requires_grad_(True)
+    _attn_ref(qq, B, N, heads).backward(dout.double())
+    out, img = ops.attention_grad(qkv.to(DEV), o, dout.to(DEV), B, N, heads, want_split=True)
+    assert rel_l2(out, qq.grad) <= 1e-5
+    assert torch.equal(ops.join_rows(img), out)
+    assert torch.equal(ops.attention_grad(qkv.to(DEV), o, dout.to(DEV), B, N, heads), out)      # reproducible
+
+
+def test_gelu_grad_and_unfused_gelu():
+    from nested_diffusion_amd import ops
+    g = torch.Generator().manual_seed(4)
+    u = torch.randn(100, 3072, generator=g) * 3
+    dg = torch.randn(100, 3072, generator=g)
+    uu = u.double().requires_grad_(True)
+    F.gelu(uu).backward(dg.double())
+    out, img = ops.gelu_grad_split(u.to(DEV), dg.to(DEV), want_out=True)
+    assert rel_l2(out, uu.grad) <= 1e-5
+    # the image is the split of the fp32 result (values below 2^-110, e.g. gelu'(-12), do not split exactly: compare images)
+    assert torch.equal(ops.join_rows(img), ops.join_rows(ops.split_rows(out)))
+    # the unfused GELU is the fc1 epilogue's value, bit for bit
+    x = torch.randn(100, 768, generator=g).to(DEV)
+    w = ops.split_rows((torch.randn(3072, 768, generator=g) / 28).to(DEV))
+    b = (0.02 * torch.randn(3072, generator=g)).to(DEV)
+    fused = ops.gemm_split(x, w, b, act="gelu")
+    y, img = ops.gelu_split(ops.gemm_split(x, w, b), want_out=True)
+    assert torch.equal(y, fused)
+    assert torch.equal(ops.join_rows(img), ops.join_rows(ops.split_rows(fused)))
+
+
+def test_xent_head_grad():
+    from nested_diffusion_amd import ops
+    g = torch.Generator().manual_seed(5)
+    B, C, E = 32, 7, 768
+    logits = torch.randn(B, C, generator=g) * 3
+    labels = torch.randint(0, C, (B,), generator=g)
+    w = torch.randn(C, E, generator=g)
+    ll = logits.double().requires_grad_(True)
+    loss = F.cross_entropy(ll, labels, reduction="none")
+    loss.sum().backward()
+    dfeat, l = ops.xent_head_grad(logits.to(DEV), labels.to(DEV), w.to(DEV))
+    assert rel_l2(dfeat, ll.grad @ w.double()) <= 1e-5
+    assert rel_l2(l, loss.detach()) <= 1e-5
+
+
+def test_unpatchify_inverts_patchify():
+    from nested_diffusion_amd import ops
+    x = torch.randn(3, 3, 224, 224, generator=torch.Generator().manual_seed(6)).to(DEV)
+    assert torch.equal(ops.unpatchify(ops.patchify(x, 16), 3, 3, 224, 224, 16), x)
+    y = torch.randn(2, 3, 32, 64, generator=torch.Generator().manual_seed(7)).to(DEV)
+    assert torch.equal(ops.unpatchify(ops.patchify(y, 16), 2, 3, 32, 64, 16), y)
+
+
+# ---- 2. + 3. forward identity and the input gradient ------------------------------------------------------------------------------
+@pytest.mark.parametrize("which,B", [("tiny", 4), ("vitb", 4)])
+def test_input_grad(which, B, request, record_property):
+    vit, vp, heads, depth, img = request.getfixturevalue(which)
+    x = images(B, img, 21)
+    labels = torch.arange(B) % 2
+    logits, dx, loss = vit.input_grad(x.to(DEV), labels.to(DEV))
+    assert torch.equal(logits, vit.forward(x.to(DEV)))                 # the forward inside input_grad is forward(), bit for bit
+    ref_logits, g_ref = ref_grad(f64(vp), x, labels, heads, depth)
+    r = rel_l2(dx, g_ref)
+    m = float((dx.cpu().double() - g_ref).abs().max() / g_ref.abs().max())
+    record_property("grad_rel_l2", r)
+    record_property("grad_max_rel", m)
+    print(f"{which}: input gradient rel L2 {r:.3e}, max |g - g_ref| / max |g_ref| {m:.3e}")
+    assert r <= 1e-4 and m <= TAU
+    assert rel_l2(loss, F.cross_entropy(ref_logits, labels, reduction="none")) <= 1e-5
+
+
+# ---- 4. FGSM ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["tiny", "vitb"])
+def test_fgsm(which, request):
+    from nested_diffusion_amd.attack import Attack
+    vit, vp, heads, depth, img = request.getfixturevalue(which)
+    B, eps = 4, 8 / 255
+    x = images(B, img, 31)
+    labels = torch.tensor([0, 1, 1, 0])
+    _, g_ref = ref_grad(f64(vp), x, labels, heads, depth)
+    atk = Attack(eps, "FGSM", vit)
+    adv, success = atk.generate_attack(x.to(DEV), labels.to(DEV))
+    want = oracle_step(x, x, g_ref, eps, eps)
+    ok, frac = agree_except_near_zero(adv, want, g_ref)
+    assert ok and frac > 0.9
+    assert float((adv.cpu() - x).abs().max()) <= eps * (1 + 1e-6)
+    assert float(adv.min()) >= 0 and float(adv.max()) <= 1
+    assert torch.equal(success.cpu(), vit.forward(adv).argmax(1).cpu() != labels)
+    adv0, _ = Attack(0.0, "FGSM", vit).generate_attack(x.to(DEV), labels.to(DEV))
+    assert torch.equal(adv0.cpu(), x.clamp(0, 1))
+
+
+# ---- 5. PGD / LinfBIM -----------------------------------------------------------------------------------------------------------
+def test_pgd_random_start_is_keyed_on_the_image():
+    from nested_diffusion_amd import ops
+    x = images(4, 32, 41)
+    eps, seed = 8 / 255, 0x1234_5678_9ABC
+    s = ops.linf_random_start(x.to(DEV), eps, seed, first_image=0)
+    assert torch.equal(s.cpu(), oracle_random_start(x, eps, seed, 0))
+    s2 = ops.linf_random_start(x[2:4].to(DEV), eps, seed, first_image=2)
+    assert torch.equal(s2, s[2:4])
+    assert float((s.cpu() - x).abs().max()) <= eps * (1 + 1e-6)
+
+
+@pytest.mark.parametrize("kind", ["PGD", "LinfBIM"])
+def test_iterative_steps_follow_the_oracle(kind, tiny):
+    from nested_diffusion_amd.attack import Attack
+    vit, vp, heads, depth, img = tiny
+    vp64 = f64(vp)
+    B, eps = 4, 8 / 255
+    x0 = images(B, img, 51)
+    labels = torch.tensor([1, 0, 1, 0])
+    atk = Attack(eps, kind, vit, seed=7)
+    x0d, ld = x0.to(DEV), labels.to(DEV)
+    x = atk.start(x0d, first_image=0)
+    if kind == "PGD":
+        assert torch.equal(x.cpu(), oracle_random_start(x0, eps, 7, 0))
+    else:
+        assert torch.equal(x, x0d)
+    worst = 1.0
+    for _ in range(atk.steps):
+        _, g_ref = ref_grad(vp64, x, labels, heads, depth)
+        nxt = atk.step(x, x0d, ld)
+        ok, frac = agree_except_near_zero(nxt, oracle_step(x, x0, g_ref, atk.stepsize, eps), g_ref)
+        assert ok
+        worst = min(worst, frac)
+        x = nxt
+    assert worst > 0.9
+    adv, _ = atk.generate_attack(x0d, ld)
+    assert float((adv.cpu() - x0).abs().max()) <= eps * (1 + 1e-6)
+    assert float(adv.min()) >= 0 and float(adv.max()) <= 1
+    assert atk.steps == {"PGD": 40, "LinfBIM": 10}[kind]
+    assert math.isclose(atk.stepsize, {"PGD": 0.01 / 0.3, "LinfBIM": 0.2}[kind] * eps)

@@ -1,0 +1,91 @@
+"""Cost of the input gradient and of the Linf attacks at the shape of an attacked evaluation: B = 32, ViT-B/16, 224 x 224.
+
+    python tools/bench_attack.py [--batch 32] [--reps 5]
+
+Prints one JSON line: ms per VisionTransformer.forward, per input_grad and its split (the dX GEMMs and the attention backward timed
+alone at the same shapes; 'rest' = the remainder: the recording forward, LayerNorm / GELU backward, head, un-patchify), per FGSM and per
+PGD batch.  Warm-up first; forward and gradient runs alternate on the one device, medians over --reps.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, reps):
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t) * 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+    from nested_diffusion_amd import ops
+    from nested_diffusion_amd.attack import Attack
+    from nested_diffusion_amd.mapping import VisionTransformer
+    from oracle import ref_cpu
+    assert torch.cuda.is_available(), "bench_attack needs the GPU"
+    B, dev = a.batch, "cuda"
+    vit = VisionTransformer(ref_cpu.init_vit_params(embed=768, depth=12, img=224, seed=1), 12, dev)
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand(B, 3, 224, 224, generator=g).to(dev)
+    y = (torch.arange(B) % 2).to(dev)
+    wT = vit.transposed_weights()
+    M, N, E = B * 197, 197, 768
+    dy = torch.randn(M, E, device=dev)
+    dy_img = ops.split_rows(dy)
+    mid_img = ops.split_rows(torch.randn(M, 4 * E, device=dev))
+    qkv_img = ops.split_rows(torch.randn(M, 3 * E, device=dev))
+    dp_img = ops.split_rows(torch.randn(B * 196, E, device=dev))
+    qkv = torch.randn(M, 3 * E, device=dev)
+    o = ops.attention(qkv, B, N, 12)
+
+    def dx_gemms():
+        for i in range(12):
+            p = f"blocks.{i}."
+            ops.gemm_split(dy_img, wT[p + "mlp.fc2.weight"])
+            ops.gemm_split(mid_img, wT[p + "mlp.fc1.weight"])
+            ops.gemm_split(dy_img, wT[p + "attn.proj.weight"])
+            ops.gemm_split(qkv_img, wT[p + "attn.qkv.weight"])
+        ops.gemm_split(dp_img, wT["patch_embed"])
+
+    def attn_bwd():
+        for _ in range(12):
+            ops.attention_grad(qkv, o, dy, B, N, 12, want_out=False, want_split=True)
+
+    fwd = lambda: vit.forward(x)                    # noqa: E731
+    grad = lambda: vit.input_grad(x, y)             # noqa: E731
+    fgsm, pgd = Attack(8 / 255, "FGSM", vit), Attack(8 / 255, "PGD", vit)
+    for f in (fwd, grad, dx_gemms, attn_bwd, fwd, grad):
+        f()
+    tf, tg = [], []
+    for _ in range(a.reps):                          # alternate forward and gradient runs
+        tf += timed(fwd, 1)
+        tg += timed(grad, 1)
+    t_dx, t_att = timed(dx_gemms, a.reps), timed(attn_bwd, a.reps)
+    t_fgsm = timed(lambda: fgsm.generate_attack(x, y), a.reps)
+    t_pgd = timed(lambda: pgd.generate_attack(x, y), max(1, a.reps // 2))
+    med = statistics.median
+    r = {"tool": "bench_attack", "batch": B, "model": "vit_base_patch16_224", "forward_ms": med(tf), "input_grad_ms": med(tg),
+         "grad_over_forward": med(tg) / med(tf), "dx_gemms_ms": med(t_dx), "attention_bwd_ms": med(t_att),
+         "rest_ms": med(tg) - med(t_dx) - med(t_att), "fgsm_batch_ms": med(t_fgsm), "pgd_batch_ms": med(t_pgd),
+         "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(r))
+
+
+if __name__ == "__main__":
+    main()
