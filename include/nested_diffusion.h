@@ -414,9 +414,11 @@ int nd_report(const float *piw_dev, const float *var_dev, const float *prob_mean
  *                         dqkv fp32 [B*N, 3*heads*64] and / or its frag32b3 image.  P is recomputed from q, k; one workgroup per
  *                         (image, head), no atomics (bitwise reproducible).  1 <= N <= 208, d = 64.
  *   nd_xent_head_bwd      d = softmax(logits) - onehot(label) (gradient of the summed cross-entropy), dfeat [B, E] = d . head_w
- *                         ([C, E]); loss [B] (may be NULL) = logsumexp(logits) - logits[label].  C <= 1024.
+ *                         ([C, E]); loss [B] (may be NULL) = logsumexp(logits) - logits[label].  C <= 1024.  d at the label is
+ *                         p - 1 in fp32: 0 once 1 - p < 2^-24, as in torch's fp32 softmax.
  *   nd_unpatchify         the exact inverse permutation of nd_patchify: cols [B*(H/p)*(W/p), Cin*p*p] -> img [B, Cin, H, W].
- *   nd_linf_step          out = clip(x0 + clip(x + alpha * sign(grad) - x0, -eps, eps), lo, hi), sign(0) = 0, each operation one
+ *   nd_linf_step          out = clip(x0 + clip(x + alpha * sign(grad) - x0, -eps, eps), lo, hi), sign(0) = 0 and a NaN
+ *                         gradient is no step (sign(NaN) = 0, where torch.sign gives NaN), each operation one
  *                         rounded fp32 op in this order (foolbox: step, project, clip to the bounds).  grad NULL: no step (with
  *                         lo = -inf, hi = inf this is foolbox's final clip_perturbation).  n elements.
  *   nd_linf_random_start  out = clip(x0 + eps * w, lo, hi) for B images of per_image elements (per_image % 4 == 0).  Element 4q + e of

@@ -339,6 +339,8 @@ __global__ __launch_bounds__(ATB_THREADS) void k_attention_bwd(const float* __re
 // ---------------------------------------------------------------------------------------------
 // Cross-entropy and head: d = softmax(logits) - onehot(label) (foolbox: crossentropy(logits, labels).sum()), dfeat = d . head_w
 // ([C, E] row-major), loss = logsumexp(logits) - logits[label].  One workgroup per image.
+// d is formed in fp32 as p - 1 at the label: once 1 - p_y < 2^-24 it is 0 there, as in torch's fp32 softmax and the foolbox loop.
+// The label's own term joins the sum last: summed in a lane, its e^0 = 1 of a confident head made every later term round at ulp(1).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_xent_head_bwd(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                        const float* __restrict__ w, float* __restrict__ dfeat, float* __restrict__ loss,
@@ -354,10 +356,11 @@ __global__ __launch_bounds__(256) void k_xent_head_bwd(const float* __restrict__
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
         float s = 0.f;
-        for (int c = t; c < C; c += 64) s += expf(l[c] - mx);
+        for (int c = t; c < C; c += 64)
+            if (c != y) s += expf(l[c] - mx);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if (t == 0) { red[0] = mx; red[1] = s; }
+        if (t == 0) { red[0] = mx; red[1] = (y >= 0 && y < C) ? s + expf(l[y] - mx) : s; }
     }
     __syncthreads();
     const float mx = red[0], inv = 1.0f / red[1];

@@ -174,8 +174,12 @@ class VisionTransformer:
         then the gradient of crossentropy(logits, labels).sum() -- foolbox's loss -- with respect to the input image x [B, 3, H, W],
         and the per-image cross-entropy."""
         x = ops._f32(x, "x")
-        wT = self.transposed_weights()
         B, _, H, W = x.shape
+        n_tok = (H // self.patch) * (W // self.patch) + 1
+        if n_tok > ops.ATTENTION_BWD_MAX_TOKENS:         # refused before the forward runs, not by the first attention backward after it
+            raise _lib.NdError(f"input_grad: the attention backward takes N <= {ops.ATTENTION_BWD_MAX_TOKENS} tokens per image "
+                               f"(N={n_tok} for {H} x {W} images, patch {self.patch})")
+        wT = self.transposed_weights()
         tok = self._tokens(x)
         N = tok.shape[0] // B
         recs = []

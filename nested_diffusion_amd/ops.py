@@ -377,6 +377,9 @@ def gelu_grad_split(u: torch.Tensor, dg: torch.Tensor, want_out: bool = False):
     return _image_or_tensor(out, osp, want_out, True)
 
 
+ATTENTION_BWD_MAX_TOKENS = 208      # ATB_NMAX of csrc/nd_vit_grad.hip: the keys per (image, head) k_attention_bwd holds in LDS
+
+
 def attention_grad(qkv: torch.Tensor, o: torch.Tensor, dout: torch.Tensor, B: int, N: int, heads: int, want_out: bool = True,
                    want_split: bool = False):
     """dqkv [B*N, 3*heads*64] of o = softmax(q k^T / 8) v (timm layout) given dout = dL/do; fp32, its frag32b3 image, or both."""

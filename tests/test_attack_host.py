@@ -92,3 +92,26 @@ def test_header_and_signatures_carry_the_gradient_entry_points():
     assert "ND_LINF_START_TAG 0x41544B31u" in hdr
     from nested_diffusion_amd import build
     assert "nd_vit_grad.hip" in build.SOURCES
+
+
+def test_gradient_kernels_refuse_bad_arguments_before_any_launch():
+    """The argument checks of the gradient / attack entry points return ND_ERR_ARG with an nd_last_error text before any HIP call
+    (dummy non-NULL pointers: nothing is dereferenced)."""
+    from nested_diffusion_amd import _lib, build
+    build.build()
+    lib = _lib.load()
+    P = 4096                                                       # a dummy non-NULL address, never dereferenced
+    cases = [
+        (lambda: lib.nd_attention_bwd(P, P, P, P, None, 2, 0, 12, None), rb"1 <= N <= 208.*N=0"),
+        (lambda: lib.nd_attention_bwd(P, P, P, P, None, 2, 209, 12, None), rb"1 <= N <= 208.*N=209"),
+        (lambda: lib.nd_attention_bwd(P, P, P, P, None, 2, 197, 0, None), rb"heads >= 1"),
+        (lambda: lib.nd_layernorm_bwd(P, P, P, None, P, None, 4, 6, 1e-6, None), rb"dim % 4 == 0, 4 <= dim <= 2048"),
+        (lambda: lib.nd_layernorm_bwd(P, P, P, None, P, None, 4, 2052, 1e-6, None), rb"dim % 4 == 0, 4 <= dim <= 2048"),
+        (lambda: lib.nd_layernorm_bwd(P, P, P, None, None, P, 4, 36, 1e-6, None), rb"split \(frag32b3\) output needs dim % 32 == 0"),
+        (lambda: lib.nd_xent_head_bwd(P, P, P, P, P, 2, 1025, 768, None), rb"C <= 1024 \(C=1025\)"),
+        (lambda: lib.nd_unpatchify(P, P, 2, 3, 24, 24, 6, None), rb"patch size must be a multiple of 4"),
+        (lambda: lib.nd_linf_random_start(P, P, 2, 6, 1, 0, 0, 0.1, 0.0, 1.0, None), rb"per_image % 4 == 0"),
+    ]
+    for call, msg in cases:
+        assert call() == -1, msg                                   # ND_ERR_ARG
+        assert re.search(msg, lib.nd_last_error()), (msg, lib.nd_last_error())
