@@ -45,6 +45,41 @@ __device__ __forceinline__ float nd_softplus(float x) {
     return x > 20.0f ? x : r;
 }
 
+// LayerNorm statistics of one row held by a wave (float4 v[i] at column (i * 64 + lane) * 4; entries past dim are zeros): the two-pass
+// mean and centred variance, output ((x - mean) - c) * rstd * gamma + beta.  c = sum(x - mean) / dim is the part of the true mean the
+// rounded fp32 mean misses; a rounded mean is off by up to half an ulp of |mean|, which a constant row turned into +-ulp * rstd
+// (rstd = eps^-1/2 = 1000) instead of 0, and a row of mean 1e4 and spread 1e-2 into a shift of 5 % of its spread.  c is applied (with
+// var = (sum (x - mean)^2 - c * sum(x - mean)) / dim) only where it matters -- |c| * rstd > 2^-18, or a variance below eps -- and is 0
+// elsewhere: a row below both thresholds keeps the plain two-pass values bit for bit (95-99 % of randn * 3 + 1 rows; the others move by
+// an ulp or two).  c and rstd are wave-uniform (butterfly sums).
+template <int VPL>
+__device__ __forceinline__ void nd_ln_stats(const float4 (&v)[VPL], int lane, int dim, float eps, float& mean, float& c, float& rstd) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    mean = s / (float)dim;
+    float sd = 0.f, q = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+        if ((i * 64 + lane) * 4 < dim) {
+            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
+            q += (a * a + b * b) + (cc * cc + d * d);
+            sd += (a + b) + (cc + d);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        q += __shfl_xor(q, off, 64);
+        sd += __shfl_xor(sd, off, 64);
+    }
+    rstd = 1.0f / sqrtf(q / (float)dim + eps);
+    c = sd / (float)dim;
+    if (fabsf(c) * rstd > 0x1p-18f || q / (float)dim < eps) rstd = 1.0f / sqrtf(fmaxf(__builtin_fmaf(-sd, c, q), 0.f) / (float)dim + eps);
+    else c = 0.f;
+}
+
 // exp(x) for x <= 0 (softmax arguments), ~1 ulp: exp2 of the product x*log2(e) carried in two pieces (t rounded + its exact
 // residual + the low part of log2 e), first-order correction on the result.  v_exp_f32 is the only transcendental; no range
 // handling is needed below zero (underflow flushes to 0, as the softmax wants).  x must be finite.

@@ -249,7 +249,8 @@ extern "C" int nd_gemm_bias_act(const float* x, const void* w, const float* bias
 }
 
 // ---------------------------------------------------------------------------------------------
-// LayerNorm over the last dim; one wave per row, two-pass (mean, then centred variance) in registers.
+// LayerNorm over the last dim; one wave per row, two-pass (mean, then centred variance) in registers (nd_ln_stats,
+// nd_common.hpp).
 // ---------------------------------------------------------------------------------------------
 // SPLIT: the result is written as a frag32b3 image (csrc/nd_b9.hpp) -- the input form of the Linear layer that follows every
 // LayerNorm of a ViT block -- instead of fp32 row-major: a lane's 4 consecutive columns are three 8-byte pieces.
@@ -261,28 +262,13 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
     if (row >= rows) return;
     const float* p = x + (size_t)row * dim;
     float4 v[VPL];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const int c = (i * 64 + lane) * 4;
         v[i] = c < dim ? *reinterpret_cast<const float4*>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)dim;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < dim) {
-            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)dim + eps);
+    float mean, cm, rstd;
+    nd_ln_stats<VPL>(v, lane, dim, eps, mean, cm, rstd);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const int c = (i * 64 + lane) * 4;
@@ -290,10 +276,10 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
             const float4 g = *reinterpret_cast<const float4*>(gamma + c);
             const float4 b = *reinterpret_cast<const float4*>(beta + c);
             float4 o;
-            o.x = (v[i].x - mean) * rstd * g.x + b.x;
-            o.y = (v[i].y - mean) * rstd * g.y + b.y;
-            o.z = (v[i].z - mean) * rstd * g.z + b.z;
-            o.w = (v[i].w - mean) * rstd * g.w + b.w;
+            o.x = ((v[i].x - mean) - cm) * rstd * g.x + b.x;
+            o.y = ((v[i].y - mean) - cm) * rstd * g.y + b.y;
+            o.z = ((v[i].z - mean) - cm) * rstd * g.z + b.z;
+            o.w = ((v[i].w - mean) - cm) * rstd * g.w + b.w;
             if (SPLIT) nd_b9_store4(reinterpret_cast<bf16x8*>(out), dim >> 5, row, c, o.x, o.y, o.z, o.w);
             else *reinterpret_cast<float4*>(out + (size_t)row * dim + c) = o;
         }
@@ -314,30 +300,15 @@ __global__ __launch_bounds__(1024) void k_layernorm_split16(const float* __restr
     {
         const int row = blockIdx.x * 16 + r16;
         float4 v[VPL];
-        float s = 0.f;
         const bool live = row < rows;
         const float* p = x + (size_t)(live ? row : 0) * dim;
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             const int c = (i * 64 + lane) * 4;
             v[i] = (live && c < dim) ? *reinterpret_cast<const float4*>(p + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        const float mean = s / (float)dim;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < VPL; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < dim) {
-                const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-                q += (a * a + b * b) + (cc * cc + d * d);
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-        const float rstd = 1.0f / sqrtf(q / (float)dim + eps);
+        float mean, cm, rstd;
+        nd_ln_stats<VPL>(v, lane, dim, eps, mean, cm, rstd);
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
             const int c = (i * 64 + lane) * 4;
@@ -345,10 +316,10 @@ __global__ __launch_bounds__(1024) void k_layernorm_split16(const float* __restr
                 const float4 g = *reinterpret_cast<const float4*>(gamma + c);
                 const float4 b = *reinterpret_cast<const float4*>(beta + c);
                 float o[4];
-                o[0] = live ? (v[i].x - mean) * rstd * g.x + b.x : 0.f;
-                o[1] = live ? (v[i].y - mean) * rstd * g.y + b.y : 0.f;
-                o[2] = live ? (v[i].z - mean) * rstd * g.z + b.z : 0.f;
-                o[3] = live ? (v[i].w - mean) * rstd * g.w + b.w : 0.f;
+                o[0] = live ? ((v[i].x - mean) - cm) * rstd * g.x + b.x : 0.f;
+                o[1] = live ? ((v[i].y - mean) - cm) * rstd * g.y + b.y : 0.f;
+                o[2] = live ? ((v[i].z - mean) - cm) * rstd * g.z + b.z : 0.f;
+                o[3] = live ? ((v[i].w - mean) - cm) * rstd * g.w + b.w : 0.f;
                 bf16x4 p1, p2, p3;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

@@ -31,7 +31,7 @@ int nd_set_err(int code, const char* fmt, ...);
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm backward, one wave per row: dx = rstd * (gg - mean(gg) - xh * mean(gg * xh)) (+ res), gg = g * gamma, xh = (x - mean) * rstd.
-// mean and rstd are recomputed exactly as k_layernorm (nd_vit.hip) computes them.
+// The statistics are recomputed exactly as k_layernorm (nd_vit.hip) computes them (nd_ln_stats).
 // ---------------------------------------------------------------------------------------------
 template <int VPL>
 __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ g,
@@ -41,28 +41,13 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__
     if (row >= rows) return;
     const size_t base = (size_t)row * dim;
     float4 v[VPL], gg[VPL];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const int c = (i * 64 + lane) * 4;
         v[i] = c < dim ? *reinterpret_cast<const float4*>(x + base + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)dim;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < dim) {
-            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)dim + eps);
+    float mean, cm, rstd;
+    nd_ln_stats<VPL>(v, lane, dim, eps, mean, cm, rstd);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -71,7 +56,7 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__
             const float4 gv = *reinterpret_cast<const float4*>(g + base + c);
             const float4 w = *reinterpret_cast<const float4*>(gamma + c);
             gg[i] = make_float4(gv.x * w.x, gv.y * w.y, gv.z * w.z, gv.w * w.w);
-            v[i] = make_float4((v[i].x - mean) * rstd, (v[i].y - mean) * rstd, (v[i].z - mean) * rstd, (v[i].w - mean) * rstd);
+            v[i] = make_float4(((v[i].x - mean) - cm) * rstd, ((v[i].y - mean) - cm) * rstd, ((v[i].z - mean) - cm) * rstd, ((v[i].w - mean) - cm) * rstd);
             s1 += (gg[i].x + gg[i].y) + (gg[i].z + gg[i].w);
             s2 += (gg[i].x * v[i].x + gg[i].y * v[i].y) + (gg[i].z * v[i].z + gg[i].w * v[i].w);
         }
