@@ -442,6 +442,45 @@ int nd_linf_step(const float *x_dev, const float *x0_dev, const float *grad_dev,
 int nd_linf_random_start(const float *x0_dev, float *out_dev, int B, size_t per_image, uint64_t seed, uint32_t first_image,
                          uint32_t restart, float eps, float lo, float hi, void *stream);
 
+/* ---- AutoAttack's APGD-CE, Linf (autopgd_base.py attack_single_run; the listing: nested_diffusion_amd/autoattack.py).  B images of
+ * per_image fp32 elements (per_image % 4 == 0, 1 <= B <= 65535, images 16-byte aligned); every operation one rounded fp32 op in the
+ * listing's order (contraction off), so a float32 restatement on the host reproduces every array bit for bit.  No entry point
+ * allocates, copies synchronously or synchronises: an iteration (input gradient, control, update) can be captured.
+ *   nd_apgd_random_start  out = clip(x0 + eps * (t / (m + 1e-12)), lo, hi).  Element 4q + e of row b draws word e of Philox4x32-10 with
+ *                         key = (seed low word, seed high word) and counter = (index[b] (low word), q, restart, ND_APGD_START_TAG),
+ *                         t = 2u - 1 as in nd_linf_random_start (exact); m = max |t| over the row (exact in any order).  index: int64
+ *                         [B], the GLOBAL image index of each row, so a row of a compacted subset (a restart over the images not yet
+ *                         fooled) draws what it draws in the full batch.  m_ws: B uint32 of workspace (zeroed here, on the stream).
+ *   nd_apgd_control       per-image state of one iteration, one thread per image.  iter = -1 initialises from the start point:
+ *                         acc = pred, loss_best = loss_best_last_check = loss, reduced_last_check = 1, step = step0 (2 eps),
+ *                         loss_steps [n_iter, B] = 0, flags = 0.  0 <= iter < n_iter: pred = (argmax logits == label; the first maximal
+ *                         index, a NaN logit never wins), acc &= pred, loss_steps[iter] = loss, improved = loss > loss_best (then
+ *                         loss_best = loss); k > 0 is a checkpoint of length k (the host passes the fixed schedule, 0 <= k <= iter+1):
+ *                         cnt = #{c < k : loss_steps[iter-c] > loss_steps[iter-c-1]} (row -1 is row n_iter-1, torch's negative index),
+ *                         osc = cnt <= k * rho || (!reduced_last_check && loss_best_last_check >= loss_best), reduced_last_check = osc,
+ *                         loss_best_last_check = loss_best, and where osc: step /= 2 and restore.  flags [B] int32 =
+ *                         ND_APGD_NOT_PRED | ND_APGD_IMPROVED | ND_APGD_RESTORE.  logits [B, C] fp32 (C <= 1024), labels int64,
+ *                         loss [B]; step, loss_best, loss_best_last_check fp32 [B]; reduced_last_check, acc int32 [B].
+ *   nd_apgd_update        per element of row b with flags f = flags[b] (flags NULL: none): NOT_PRED: x_best_adv = x_adv; IMPROVED:
+ *                         x_best = x_adv, grad_best = grad; RESTORE: the iterate becomes x_best and its gradient grad_best (grad itself
+ *                         is read-only).  do_step: then the momentum step with coefficient a (1 for the first step, 0.75 after):
+ *                         g2 = xa - x_adv_old, x_adv_old = xa, z = clip(min(max(xa + step[b] * sign(g), x - eps), x + eps), 0, 1),
+ *                         x_adv = clip(min(max((xa + (z - xa) * a) + g2 * (1 - a), x - eps), x + eps), 0, 1), sign(NaN) = 0 (no step).
+ *                         Without the step a restored row's x_adv is written with x_best.  The first step (no flags, a = 1) expects
+ *                         x_adv_old = x_adv: g2 = 0. */
+#define ND_APGD_START_TAG 0x41504731u
+#define ND_APGD_NOT_PRED 1
+#define ND_APGD_IMPROVED 2
+#define ND_APGD_RESTORE 4
+int nd_apgd_random_start(const float *x0_dev, const int64_t *index_dev, float *out_dev, uint32_t *m_ws_dev, int B, size_t per_image,
+                         uint64_t seed, uint32_t restart, float eps, float lo, float hi, void *stream);
+int nd_apgd_control(const float *logits_dev, const int64_t *labels_dev, const float *loss_dev, float *step_dev, float *loss_best_dev,
+                    float *loss_best_last_check_dev, int32_t *reduced_last_check_dev, int32_t *acc_dev, float *loss_steps_dev,
+                    int32_t *flags_dev, int B, int C, int n_iter, int iter, int k, float rho, float step0, void *stream);
+int nd_apgd_update(const float *x_dev, float *x_adv_dev, float *x_adv_old_dev, const float *grad_dev, float *x_best_dev,
+                   float *grad_best_dev, float *x_best_adv_dev, const int32_t *flags_dev, const float *step_dev, int B, size_t per_image,
+                   float eps, float a, int do_step, void *stream);
+
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */
 /* add_noise (:272-279): out = x + z * std, z = the randn_like draw (supplied, like the sampler's noise). */

@@ -165,6 +165,9 @@ SIGNATURES = {
     "nd_unpatchify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nd_linf_step": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _vp]),
     "nd_linf_random_start": (_i, [_vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_apgd_random_start": (_i, [_vp, _vp, _vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_apgd_control": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "nd_apgd_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _i, _vp]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
 }
 

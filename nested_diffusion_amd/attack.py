@@ -32,7 +32,8 @@ LINF_ATTACKS = {
     "PGD": ("LinfProjectedGradientDescentAttack", 0.01 / 0.3, 40, True),
     "LinfBIM": ("LinfBasicIterativeAttack", 0.2, 10, False),
 }
-# the reference's other attacks: the L2 family, Carlini & Wagner and AutoAttack's APGD (utils.apply_attack's 'AUTOPGD' branch)
+# the reference's other attacks: the L2 family, Carlini & Wagner, and AutoAttack's APGD, which its Attack class has no branch for either
+# (apply_attack's 'AUTOPGD' branch takes an autoattack.AutoAttack)
 NOT_IMPLEMENTED = ("CW", "BIM", "L2PGD", "AUTOPGD")
 
 
@@ -80,9 +81,13 @@ class Attack:
 
 def apply_attack(attack_func: Attack, images_in: torch.Tensor, labels_in: torch.Tensor, attack_name: str,
                  first_image: int = 0) -> torch.Tensor:
-    """utils.py:258-269: the adversarial images of a batch (the inputs are not modified)."""
+    """utils.py:258-269: the adversarial images of a batch (the inputs are not modified).  AUTOPGD takes an autoattack.AutoAttack
+    (run_standard_evaluation with bs = the batch, as utils.py:263-266 calls it)."""
     if attack_name == "AUTOPGD":
-        raise NotImplementedError("attack 'AUTOPGD' is not implemented (AutoAttack's run_standard_evaluation)")
+        from .autoattack import AutoAttack
+        if not isinstance(attack_func, AutoAttack):
+            raise NotImplementedError("attack 'AUTOPGD' needs an autoattack.AutoAttack (AutoAttack's run_standard_evaluation)")
+        return attack_func.run_standard_evaluation(images_in.clone(), labels_in.clone(), bs=labels_in.shape[0], first_image=first_image)
     adv, _ = attack_func.generate_attack(images_in.clone(), labels_in.clone(), first_image=first_image)
     return adv
 

@@ -1,12 +1,13 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
-    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD --eps E --out ROOT \
+    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|AUTOPGD --eps E --out ROOT \
         [--preprocess grayscaled] [--seed S] [--batch_size B]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
-test split (the PGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
+test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
 as RGB uint8 = round(255 * adv), with the classes and file stems of the source: the tree data_loader_attacks reads
-(dataset_helper/chest_x_ray_dataset.py:197-227; here data.get_dataset with a *Atk<NAME> dataset name).
+(dataset_helper/chest_x_ray_dataset.py:197-227; here data.get_dataset with a *Atk<NAME> dataset name).  AUTOPGD is the reference's
+AutoAttack(vit, eps=eps, version='custom', norm='Linf', attacks_to_run=['apgd-ce']) run by run_standard_evaluation on each batch.
 """
 from __future__ import annotations
 
@@ -21,11 +22,11 @@ import torch
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="write an attacked test set (Test_attacks_<NAME>) with the GPU attacks of attack.py")
     p.add_argument("--config", type=str, required=True)
-    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD"], required=True)
+    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "AUTOPGD"], required=True)
     p.add_argument("--eps", type=float, required=True)
     p.add_argument("--out", type=str, required=True, help="root the Test_attacks_<NAME> tree is written under")
     p.add_argument("--preprocess", type=str, choices=["grayscaled", "standardized"], default="grayscaled")
-    p.add_argument("--seed", type=int, default=0, help="key of the PGD random start")
+    p.add_argument("--seed", type=int, default=0, help="key of the PGD / APGD random start")
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--dataroot", type=str, default=None)
     p.add_argument("--device", type=int, default=0)
@@ -37,6 +38,7 @@ def main(argv=None) -> int:
 
     from . import main as nd_main
     from .attack import Attack
+    from .autoattack import AutoAttack
     from .data import get_dataset
     from .mapping import VisionTransformer, load_pickled
     from .runner import CHEST
@@ -54,7 +56,10 @@ def main(argv=None) -> int:
     ckpt = "ChestXRay" if base in CHEST else "ISICSkinCancer"
     sd = load_pickled(os.path.join(config.diffusion.trained_aux_cls_ckpt_path, f"vit_base_patch16_224_{ckpt}.pth"))
     vit = VisionTransformer(sd, max(1, sd["patch_embed.proj.weight"].shape[0] // 64), device)
-    attack = Attack(args.eps, args.attack_name, vit, seed=args.seed)
+    if args.attack_name == "AUTOPGD":
+        attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
+    else:
+        attack = Attack(args.eps, args.attack_name, vit, seed=args.seed)
     out_root = os.path.join(args.out, f"Test_attacks_{args.attack_name}")
     n_ok = 0
     for start in range(0, len(ds), args.batch_size):
@@ -62,7 +67,11 @@ def main(argv=None) -> int:
         items = [ds[i] for i in idx]
         x = torch.stack([it[0] for it in items]).to(device)
         y = torch.tensor([it[1] for it in items], dtype=torch.int64, device=device)
-        adv, success = attack.generate_attack(x, y, first_image=start)
+        if args.attack_name == "AUTOPGD":
+            adv = attack.run_standard_evaluation(x, y, bs=len(idx), first_image=start)
+            success = vit.forward(adv).argmax(dim=1) != y
+        else:
+            adv, success = attack.generate_attack(x, y, first_image=start)
         n_ok += int(success.sum())
         pix = torch.round(adv.clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous().cpu().numpy()
         for k, i in enumerate(idx):

@@ -455,3 +455,116 @@ def linf_random_start(x0: torch.Tensor, eps: float, seed: int, first_image: int 
     check(_lib.load().nd_linf_random_start(ptr(x0), ptr(out), B, per, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image) & 0xFFFFFFFF,
                                            int(restart) & 0xFFFFFFFF, float(eps), float(lo), float(hi), _stream(x0)), "nd_linf_random_start")
     return out
+
+
+# ---- AutoAttack APGD-CE, Linf (include/nested_diffusion.h: nd_apgd_*; the loop: autoattack.py) ----------------------------------------
+APGD_NOT_PRED, APGD_IMPROVED, APGD_RESTORE = 1, 2, 4       # ND_APGD_* flag bits
+
+
+def _inplace(t: Optional[torch.Tensor], name: str, dtype=torch.float32, shape=None) -> Optional[torch.Tensor]:
+    """A tensor the kernel writes in place: on the GPU, of `dtype` and `shape`, and contiguous (a copy would lose the writes)."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise _lib.NdError(f"{name} must be a GPU tensor (no CPU fallback)")
+    if t.dtype != dtype:
+        raise _lib.NdError(f"{name} must be {dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (it is written in place)")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} is {tuple(t.shape)}; expected {tuple(shape)}")
+    return t
+
+
+def _per_image(x: torch.Tensor) -> Tuple[int, int]:
+    B = x.shape[0] if x.dim() else 0
+    per = x.numel() // max(B, 1)
+    if B < 1 or per % 4:
+        raise ValueError(f"need at least one image and a multiple of 4 elements per image (shape {tuple(x.shape)})")
+    return B, per
+
+
+def apgd_random_start(x0: torch.Tensor, index: torch.Tensor, eps: float, seed: int, restart: int = 0, lo: float = 0.0,
+                      hi: float = 1.0) -> torch.Tensor:
+    """APGD's start clip(x0 + eps * t / (max|t| + 1e-12), lo, hi), t = 2 U[0, 1) - 1 per element, max per image; row b draws with the key
+    (seed, index[b], element, restart), so a row of a compacted subset draws what it draws in the full batch."""
+    x0 = _f32(x0, "x0")
+    B, per = _per_image(x0)
+    index = index.to(device=x0.device, dtype=torch.int64).contiguous()
+    if tuple(index.shape) != (B,):
+        raise ValueError(f"index must be [{B}] (the global image index of each row)")
+    out = torch.empty_like(x0)
+    m_ws = torch.empty(B, dtype=torch.int32, device=x0.device)
+    check(_lib.load().nd_apgd_random_start(ptr(x0), ptr(index), ptr(out), ptr(m_ws), B, per, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(restart) & 0xFFFFFFFF, float(eps), float(lo), float(hi), _stream(x0)), "nd_apgd_random_start")
+    return out
+
+
+class ApgdState:
+    """APGD's per-image state on the device (nd_apgd_control): step, loss_best, loss_best_last_check (fp32 [B]), reduced_last_check, acc
+    (int32 [B]), loss_steps (fp32 [n_iter, B]) and the flags of the last iteration (int32 [B])."""
+
+    def __init__(self, B: int, n_iter: int, device):
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)     # noqa: E731
+        i = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)       # noqa: E731
+        self.B, self.n_iter = B, n_iter
+        self.step, self.loss_best, self.loss_best_last_check = f(B), f(B), f(B)
+        self.reduced_last_check, self.acc, self.flags = i(B), i(B), i(B)
+        self.loss_steps = f(n_iter, B)
+
+
+def apgd_control(logits: torch.Tensor, labels: torch.Tensor, loss: torch.Tensor, state: ApgdState, it: int, k: int = 0, rho: float = 0.75,
+                 step0: float = 0.0) -> torch.Tensor:
+    """APGD's per-image bookkeeping of iteration `it` (-1: initialise from the start point, step = step0), with a checkpoint of length k
+    when k > 0; updates `state` in place on the device and returns state.flags (APGD_NOT_PRED | APGD_IMPROVED | APGD_RESTORE).
+    Nothing is read back to the host."""
+    logits = _f32(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, C]")
+    B, C = logits.shape
+    if C < 1 or C > 1024:
+        raise ValueError(f"apgd control takes 1 <= C <= 1024 classes (C={C})")
+    if B != state.B:
+        raise ValueError(f"logits has {B} rows, the state {state.B}")
+    labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+    loss = _f32(loss, "loss")
+    if tuple(labels.shape) != (B,) or tuple(loss.shape) != (B,):
+        raise ValueError(f"labels and loss must be [{B}]")
+    if not -1 <= it < state.n_iter or not 0 <= k <= it + 1:
+        raise ValueError(f"need -1 <= it < n_iter and 0 <= k <= it + 1 (it={it}, k={k}, n_iter={state.n_iter})")
+    s = state
+    for name in ("step", "loss_best", "loss_best_last_check"):
+        _inplace(getattr(s, name), name, torch.float32, (B,))
+    for name in ("reduced_last_check", "acc", "flags"):
+        _inplace(getattr(s, name), name, torch.int32, (B,))
+    _inplace(s.loss_steps, "loss_steps", torch.float32, (s.n_iter, B))
+    check(_lib.load().nd_apgd_control(ptr(logits), ptr(labels), ptr(loss), ptr(s.step), ptr(s.loss_best), ptr(s.loss_best_last_check),
+                                      ptr(s.reduced_last_check), ptr(s.acc), ptr(s.loss_steps), ptr(s.flags), B, C, s.n_iter, int(it),
+                                      int(k), float(rho), float(step0), _stream(logits)), "nd_apgd_control")
+    return s.flags
+
+
+def apgd_update(x: torch.Tensor, x_adv: torch.Tensor, x_adv_old: Optional[torch.Tensor], grad: torch.Tensor,
+                x_best: Optional[torch.Tensor], grad_best: Optional[torch.Tensor], x_best_adv: Optional[torch.Tensor],
+                flags: Optional[torch.Tensor], step: Optional[torch.Tensor], eps: float, a: float, do_step: bool) -> None:
+    """APGD's per-element work of one iteration, in place: the flags' copies (x_best_adv, x_best / grad_best, the restore), then with
+    do_step the momentum step of coefficient a from x_adv (or the restored x_best) to the next iterate (x_adv, x_adv_old).
+    flags None: the step alone (the first step: a = 1, with x_adv_old a copy of x_adv)."""
+    x_adv = _inplace(x_adv, "x_adv")
+    B, per = _per_image(x_adv)
+    shape = tuple(x_adv.shape)
+    grad = _inplace(grad, "grad", shape=shape)
+    if flags is not None:
+        flags = _inplace(flags, "flags", torch.int32, (B,))
+        if x_best is None or grad_best is None or x_best_adv is None:
+            raise ValueError("the flags need x_best, grad_best and x_best_adv")
+        x_best, grad_best, x_best_adv = (_inplace(t, n, shape=shape) for t, n in ((x_best, "x_best"), (grad_best, "grad_best"),
+                                                                                   (x_best_adv, "x_best_adv")))
+    if do_step:
+        if x is None or x_adv_old is None or step is None:
+            raise ValueError("a step needs x, x_adv_old and step")
+        x, x_adv_old = _inplace(x, "x", shape=shape), _inplace(x_adv_old, "x_adv_old", shape=shape)
+        step = _inplace(step, "step", shape=(B,))
+    check(_lib.load().nd_apgd_update(ptr(x) if do_step else None, ptr(x_adv), ptr(x_adv_old) if do_step else None, ptr(grad),
+                                     ptr(x_best), ptr(grad_best), ptr(x_best_adv), ptr(flags), ptr(step) if do_step else None, B, per,
+                                     float(eps), float(a), int(bool(do_step)), _stream(x_adv)), "nd_apgd_update")

@@ -4,7 +4,9 @@
 
 Prints one JSON line: ms per VisionTransformer.forward, per input_grad and its split (the dX GEMMs and the attention backward timed
 alone at the same shapes; 'rest' = the remainder: the recording forward, LayerNorm / GELU backward, head, un-patchify), per FGSM and per
-PGD batch.  Warm-up first; forward and gradient runs alternate on the one device, medians over --reps.
+PGD batch.  Warm-up first; forward and gradient runs alternate on the one device, medians over --reps.  AutoAttack APGD-CE (autoattack.py):
+ms per iteration (input_grad + nd_apgd_control + nd_apgd_update with the next step fused), the control and update kernels alone, and
+one run_standard_evaluation on a batch that no restart fools (eps = 0, labels = the clean predictions: the worst case, 5 x 101 gradients).
 """
 import argparse
 import json
@@ -36,6 +38,7 @@ def main():
     a = ap.parse_args()
     from nested_diffusion_amd import ops
     from nested_diffusion_amd.attack import Attack
+    from nested_diffusion_amd.autoattack import AutoAttack
     from nested_diffusion_amd.mapping import VisionTransformer
     from oracle import ref_cpu
     assert torch.cuda.is_available(), "bench_attack needs the GPU"
@@ -79,10 +82,36 @@ def main():
     t_dx, t_att = timed(dx_gemms, a.reps), timed(attn_bwd, a.reps)
     t_fgsm = timed(lambda: fgsm.generate_attack(x, y), a.reps)
     t_pgd = timed(lambda: pgd.generate_attack(x, y), max(1, a.reps // 2))
+    # APGD: one iteration, and its two kernels alone (at an iteration without a checkpoint, every flag as it comes)
+    eps = 8 / 255
+    st = ops.ApgdState(B, 100, dev)
+    xa = ops.apgd_random_start(x, torch.arange(B, device=dev), eps, 0)
+    logits, g0, loss = vit.input_grad(xa, y)
+    ops.apgd_control(logits, y, loss, st, -1, 0, step0=2 * eps)
+    xb, xba, gb, xo = xa.clone(), xa.clone(), g0.clone(), xa.clone()
+
+    def apgd_kernels():
+        f = ops.apgd_control(logits, y, loss, st, 1)
+        ops.apgd_update(x, xa, xo, g0, xb, gb, xba, f, st.step, eps, 0.75, True)
+
+    def apgd_iter():
+        lg, g, l = vit.input_grad(xa, y)
+        f = ops.apgd_control(lg, y, l, st, 1)
+        ops.apgd_update(x, xa, xo, g, xb, gb, xba, f, st.step, eps, 0.75, True)
+
+    for f in (apgd_kernels, apgd_iter):
+        f()
+    t_kern = [t / 20 for t in timed(lambda: [apgd_kernels() for _ in range(20)], a.reps)]
+    t_iter = timed(apgd_iter, a.reps)
+    y_clean = vit.forward(x).argmax(1)
+    aa = AutoAttack(vit, eps=0.0, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
+    t_apgd = timed(lambda: aa.run_standard_evaluation(x, y_clean, bs=B), 1)
     med = statistics.median
     r = {"tool": "bench_attack", "batch": B, "model": "vit_base_patch16_224", "forward_ms": med(tf), "input_grad_ms": med(tg),
          "grad_over_forward": med(tg) / med(tf), "dx_gemms_ms": med(t_dx), "attention_bwd_ms": med(t_att),
          "rest_ms": med(tg) - med(t_dx) - med(t_att), "fgsm_batch_ms": med(t_fgsm), "pgd_batch_ms": med(t_pgd),
+         "apgd_iter_ms": med(t_iter), "apgd_control_update_ms": med(t_kern), "apgd_kernels_over_input_grad": med(t_kern) / med(tg),
+         "apgd_worst_batch_s": med(t_apgd) / 1e3, "apgd_worst_batch_over_input_grad": med(t_apgd) / med(tg),
          "device": torch.cuda.get_device_name(0)}
     print(json.dumps(r))
 
