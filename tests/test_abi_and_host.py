@@ -320,6 +320,24 @@ def test_step_block_dispatch_threshold_and_tile_plan():
     assert lib.nd_step_plan(4096, 0, 5, 0, out) != 0 and lib.nd_step_plan(40, 32, 1, 0, out) != 0
 
 
+
+def test_step_plan_restatement_and_branch_search_without_gpu():
+    """The launch plan of the step blocks restated in tests/test_gpu_step_edges.py (cond-GEMM tile plan and k-split tail,
+    b9 / rows-head / device-table choices, eps partials, k_skinny row passes) against nd_step_plan / nd_skinny_plan at the
+    256 CUs the library assumes without a device, over a sweep and over every shape its branch search picks; the searched
+    shapes reach every branch that file must cover."""
+    from test_gpu_step_edges import all_case_shapes, assert_plan_matches_library, check_case_coverage, step_launch
+    shapes = all_case_shapes(256)
+    for L in shapes.values():
+        assert_plan_matches_library(L)
+    check_case_coverage(shapes)
+    for F in (16, 272, 1056, 4160, 4224):
+        for M in (1, 64, 65, 96, 128, 129, 161, 207, 640, 1400):
+            for nm in (1, 3, 5, 8, 9, 11):
+                for half in ((False, True) if F % 32 == 0 else (False,)):
+                    assert_plan_matches_library(step_launch(F, M, nm, half, 256))
+    assert {L["split"] for L in shapes.values() if L["kernel"] == "k_cond_gemm_b9"} >= {1, 2, 3, 4}
+
 def test_step_gemm_loops_keep_counted_waits():
     """ISA check (no GPU): every software-pipelined k_skinny loop must wait with a counted vmcnt and contain no flat_load --
     a pending flat load (pointer read out of a descriptor table without an address-space cast) or an uncountable load before
