@@ -291,6 +291,8 @@ int nd_softmax_rows(const float *x_dev, float *out_dev, int rows, int C, void *s
  *   prob_out [B, C]  = mean_s softmax(-(y-1)^2 / temperature)   (convert_to_prob + compute_ensemble_confidence,
  *                      classification_train_separately.py:392-398, 425-447)
  *   vote_out [B] int64 = mode_s argmax_c y  (ties -> smallest label; majority_voting_for_mc_samples :51-68)
+ *   Non-finite y follow torch: argmax treats a NaN as the maximum and takes the first one; a sample whose logits hold a NaN
+ *   or are all -inf (every |y| so large that (y-1)^2 overflows) has NaN probabilities, and so has the image's prob_out row.
  *   probs_out optional [S, B, C]: per-sample probabilities (what the reference leaves in mc_samples, quirk Q4) */
 int nd_aggregate(const float *samples_dev, float *prob_out_dev, int64_t *vote_out_dev, float *probs_out_dev,
                  int S, int B, int C, float temperature, void *stream);
@@ -385,7 +387,9 @@ int nd_predict_batch(nd_handle h, nd_cond c, const float *images_dev, const floa
 /* Per-image spread of the S = K*mc per-sample probabilities (what the reference keeps in pred_mc, quirk Q4):
  *   piw_out[B,C] = quantile(q_hi) - quantile(q_lo) over the samples (torch.quantile semantics: linear
  *                  interpolation at rank q*(S-1));  compute_mean_piws_for_class :108-114 uses 0.025 / 0.975
- *   var_out[B,C] = unbiased variance over the samples;  calculate_variances :166-172
+ *   var_out[B,C] = unbiased variance over the samples (NaN at S = 1);  calculate_variances :166-172
+ *   A NaN among the S values of one (b, c) gives NaN piw_out and var_out for that (b, c), as torch.quantile and var do; every
+ *   other (b, c) is unaffected.
  * probs_dev [S,B,C]. */
 int nd_sample_stats(const float *probs_dev, float *piw_out_dev, float *var_out_dev, int S, int B, int C,
                     float q_lo, float q_hi, void *stream);
@@ -491,7 +495,8 @@ int nd_img_brightness(const float *x_dev, float *out_dev, size_t n, float k, voi
 int nd_img_contrast(const float *x_dev, float *out_dev, float *mean_ws_dev, int B, size_t per_image, float k, void *stream);
 /* torch interpolate(mode='bilinear', align_corners=False) [B,C,Hi,Wi] -> [B,C,Ho,Wo]: down_up_sample (:372-387) is two
  * calls.  With crop_dev != NULL ([B][2] int32 = top, left) the source is the crop_size x crop_size window of each
- * image: random_crop_and_resize (:282-312; torchvision Resize on tensors = the same interpolate). */
+ * image: random_crop_and_resize (:282-312; torchvision Resize on tensors = the same interpolate).  The source coordinate
+ * scale * (dst + 0.5) - 0.5 is one fused multiply-add, as in torch's builds. */
 int nd_img_resize_bilinear(const float *x_dev, float *out_dev, int B, int C, int Hi, int Wi, int Ho, int Wo,
                            const int32_t *crop_dev, int crop_size, void *stream);
 /* random_cover_new (:315-349): zero n_rects squares of side `side` per image, in place; rects_dev [B][n_rects][2]

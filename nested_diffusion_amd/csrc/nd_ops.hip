@@ -204,7 +204,8 @@ __global__ void k_softmax_rows(const float* __restrict__ x, float* __restrict__ 
 }
 
 extern "C" int nd_softmax_rows(const float* x, float* out, int rows, int C, void* stream) {
-    if (!x || !out || rows < 1 || C < 1) return nd_set_err(ND_ERR_ARG, "bad softmax arguments");
+    if (!x || !out) return nd_set_err(ND_ERR_ARG, "softmax: NULL tensor");
+    if (rows < 1 || C < 1) return nd_set_err(ND_ERR_ARG, "softmax needs rows, C >= 1 (rows=%d, C=%d)", rows, C);
     hipLaunchKernelGGL(k_softmax_rows, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, x, out, rows, C);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
@@ -213,7 +214,9 @@ extern "C" int nd_softmax_rows(const float* x, float* out, int rows, int C, void
 // ---- aggregation (classification_train_separately.py:51-68, 392-398, 425-447) ------------------
 // One thread per image b: loops the S samples in order (member-major then trial), so the mean is a
 // fixed-order sum.  convert_to_prob: softmax(-(y-1)^2 / temperature); vote: mode of argmax over the
-// raw y_0 (first maximum = smallest label on ties, as torch.argmax / torch.unique+counts.argmax).
+// raw y_0 (first maximum = smallest label on ties, as torch.argmax / torch.unique+counts.argmax; a NaN counts as the
+// maximum and the first NaN is taken, as torch.argmax does).  A NaN or an all-(-inf) logit row gives NaN probabilities
+// for that sample and so for the image's mean, as torch.softmax does.
 #define ND_AGG_MAX_C 16
 __global__ void k_aggregate(const float* __restrict__ samples, float* __restrict__ prob, long long* __restrict__ vote,
                             float* __restrict__ probs, int S, int B, int C, float temperature) {
@@ -231,7 +234,7 @@ __global__ void k_aggregate(const float* __restrict__ samples, float* __restrict
         for (int c = 0; c < C; ++c) {
             const float d = y[c] - 1.0f;
             lg[c] = d * d * (-1.0f) / temperature;
-            if (y[c] > best) { best = y[c]; am = c; }
+            if (y[c] > best || (y[c] != y[c] && best == best)) { best = y[c]; am = c; }
         }
         cnt[am]++;
         float mx = lg[0];
@@ -253,8 +256,8 @@ __global__ void k_aggregate(const float* __restrict__ samples, float* __restrict
 extern "C" int nd_aggregate(const float* samples, float* prob_out, int64_t* vote_out, float* probs_out, int S, int B, int C,
                             float temperature, void* stream) {
     if (!samples || !prob_out || !vote_out) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (S < 1 || B < 1 || C < 1 || C > ND_AGG_MAX_C) return nd_set_err(ND_ERR_ARG, "S,B >= 1 and 1 <= C <= %d required", ND_AGG_MAX_C);
-    if (!(temperature > 0.f)) return nd_set_err(ND_ERR_ARG, "temperature must be > 0");
+    if (S < 1 || B < 1 || C < 1 || C > ND_AGG_MAX_C) return nd_set_err(ND_ERR_ARG, "S,B >= 1 and 1 <= C <= %d required (S=%d, B=%d, C=%d)", ND_AGG_MAX_C, S, B, C);
+    if (!(temperature > 0.f)) return nd_set_err(ND_ERR_ARG, "temperature must be > 0 (temperature=%g)", (double)temperature);
     hipLaunchKernelGGL(k_aggregate, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, prob_out, (long long*)vote_out,
                        probs_out, S, B, C, temperature);
     HIP_CHECK(hipGetLastError());
@@ -265,7 +268,9 @@ extern "C" int nd_aggregate(const float* samples, float* prob_out, int64_t* vote
 // ---- reporting tail (classification_train_separately.py:102-174, 413-423, 801-815) ---------------
 // One wave per (image, class): the S per-sample values go to LDS; every lane ranks its elements by counting
 // (stable: ties broken by index), the four order statistics needed by the two interpolated quantiles are
-// picked by rank.  Variance: two-pass (mean, then centred squares), unbiased.
+// picked by rank.  Variance: two-pass (mean, then centred squares), unbiased.  A NaN among the S values has no rank (it
+// compares false with everything), so the picks are not all written: such a (b, c) gets NaN PIW, as torch.quantile
+// gives, and pick[] is not read; its variance is NaN through the sums.
 #define ND_STATS_MAXS 4096
 __global__ __launch_bounds__(64) void k_sample_stats(const float* __restrict__ probs, float* __restrict__ piw, float* __restrict__ var,
                                                      int S, int B, int C, float q_lo, float q_hi) {
@@ -279,9 +284,11 @@ __global__ __launch_bounds__(64) void k_sample_stats(const float* __restrict__ p
     const int k0 = (int)floorf(r_lo), k2 = (int)floorf(r_hi);
     const int k1 = min(k0 + 1, S - 1), k3 = min(k2 + 1, S - 1);
     float sum = 0.f;
+    int has_nan = 0;
     for (int i = lane; i < S; i += 64) {
         const float vi = v[i];
         sum += vi;
+        has_nan |= vi != vi;
         int rank = 0;
         for (int j = 0; j < S; ++j) rank += (v[j] < vi) || (v[j] == vi && j < i);
         if (rank == k0) pick[0] = vi;
@@ -290,7 +297,7 @@ __global__ __launch_bounds__(64) void k_sample_stats(const float* __restrict__ p
         if (rank == k3) pick[3] = vi;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    for (int off = 32; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, 64); has_nan |= __shfl_xor(has_nan, off, 64); }
     const float mean = sum / (float)S;
     float sq = 0.f;
     for (int i = lane; i < S; i += 64) { const float d = v[i] - mean; sq += d * d; }
@@ -298,19 +305,21 @@ __global__ __launch_bounds__(64) void k_sample_stats(const float* __restrict__ p
     for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off, 64);
     __syncthreads();
     if (lane == 0) {
+        var[bc] = S > 1 ? sq / (float)(S - 1) : NAN;
+        if (has_nan) { piw[bc] = NAN; return; }
         // torch.lerp(a, b, w): a + w*(b-a) for w < 0.5, else b - (b-a)*(1-w)
         const float w_lo = r_lo - (float)k0, w_hi = r_hi - (float)k2;
         const float lo = w_lo < 0.5f ? pick[0] + w_lo * (pick[1] - pick[0]) : pick[1] - (pick[1] - pick[0]) * (1.0f - w_lo);
         const float hi = w_hi < 0.5f ? pick[2] + w_hi * (pick[3] - pick[2]) : pick[3] - (pick[3] - pick[2]) * (1.0f - w_hi);
         piw[bc] = hi - lo;
-        var[bc] = S > 1 ? sq / (float)(S - 1) : NAN;
     }
 }
 
 extern "C" int nd_sample_stats(const float* probs, float* piw, float* var, int S, int B, int C, float q_lo, float q_hi, void* stream) {
     if (!probs || !piw || !var) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (S < 1 || S > ND_STATS_MAXS || B < 1 || C < 1) return nd_set_err(ND_ERR_ARG, "need 1 <= S <= %d, B,C >= 1", ND_STATS_MAXS);
-    if (!(q_lo >= 0.f && q_lo <= q_hi && q_hi <= 1.f)) return nd_set_err(ND_ERR_ARG, "need 0 <= q_lo <= q_hi <= 1");
+    if (S < 1 || S > ND_STATS_MAXS || B < 1 || C < 1) return nd_set_err(ND_ERR_ARG, "need 1 <= S <= %d, B,C >= 1 (S=%d, B=%d, C=%d)", ND_STATS_MAXS, S, B, C);
+    if (!(q_lo >= 0.f && q_lo <= q_hi && q_hi <= 1.f))
+        return nd_set_err(ND_ERR_ARG, "need 0 <= q_lo <= q_hi <= 1 (q_lo=%g, q_hi=%g)", (double)q_lo, (double)q_hi);
     hipLaunchKernelGGL(k_sample_stats, dim3(B * C), dim3(64), 0, (hipStream_t)stream, probs, piw, var, S, B, C, q_lo, q_hi);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
@@ -373,8 +382,8 @@ __global__ __launch_bounds__(256) void k_report(const float* __restrict__ piw, c
 extern "C" int nd_report(const float* piw, const float* var, const float* pm, const int64_t* vote, const int64_t* target, float* out,
                          int N, int C, float temperature, int n_bins, void* stream) {
     if (!piw || !var || !pm || !vote || !target || !out) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (N < 1 || C < 1 || C > 16 || n_bins < 1 || n_bins > ND_REPORT_MAXBINS) return nd_set_err(ND_ERR_ARG, "need N >= 1, 1 <= C <= 16, 1 <= n_bins <= %d", ND_REPORT_MAXBINS);
-    if (!(temperature > 0.f)) return nd_set_err(ND_ERR_ARG, "temperature must be > 0");
+    if (N < 1 || C < 1 || C > 16 || n_bins < 1 || n_bins > ND_REPORT_MAXBINS) return nd_set_err(ND_ERR_ARG, "need N >= 1, 1 <= C <= 16, 1 <= n_bins <= %d (N=%d, C=%d, n_bins=%d)", ND_REPORT_MAXBINS, N, C, n_bins);
+    if (!(temperature > 0.f)) return nd_set_err(ND_ERR_ARG, "temperature must be > 0 (temperature=%g)", (double)temperature);
     hipLaunchKernelGGL(k_report, dim3(1), dim3(256), 0, (hipStream_t)stream, piw, var, pm, (const long long*)vote, (const long long*)target, out,
                        N, C, temperature, n_bins);
     HIP_CHECK(hipGetLastError());

@@ -109,7 +109,8 @@ extern "C" int nd_philox_normal(float* out_dev, int n_members, int T, int B, int
     if (!out_dev) return nd_set_err(ND_ERR_ARG, "out_dev is NULL");
     // counter word 1 = trial (16 bits) | member (8 bits) | class-quad (8 bits)
     if (n_members < 1 || n_members > 255 || T < 1 || B < 1 || mc < 1 || mc > 65535 || C < 1 || C > 1024)
-        return nd_set_err(ND_ERR_ARG, "need 1 <= n_members <= 255, 1 <= mc <= 65535, T, B >= 1, 1 <= C <= 1024");
+        return nd_set_err(ND_ERR_ARG, "need 1 <= n_members <= 255, 1 <= mc <= 65535, T, B >= 1, 1 <= C <= 1024 (n_members=%d, T=%d, B=%d, mc=%d, C=%d)",
+                          n_members, T, B, mc, C);
     HIP_CHECK(nd_launch_philox_normal(out_dev, nullptr, seed, batch_counter, first_image, 0, n_members, T, B, mc, C, (hipStream_t)stream));
     return ND_OK;
 }

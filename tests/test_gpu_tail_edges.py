@@ -1,0 +1,729 @@
+"""Edge shapes of the kernels on either side of the sampler: aggregation and row softmax (k_aggregate, k_softmax_rows), the reporting
+tail (k_sample_stats, k_report; csrc/nd_ops.hip), the five image kernels (csrc/nd_image.hip) and the in-library noise (k_philox_normal;
+csrc/nd_rng.hip).  The argument rejections of the same operators are in tests/test_tail_host.py (no GPU needed).
+
+What this covers
+- k_aggregate: S = 1, the 64-thread block boundary, a second and third block and the last block's tail, C up to ND_AGG_MAX_C = 16, three
+  temperatures; vote ties; extreme finite y (logits to -7e5, exact 0 / 1 probabilities); NaN / +-inf / overflowing y against the float32
+  oracle (torch.argmax takes the first NaN as the maximum; a NaN or all -inf logit row is a NaN softmax row), clean rows bit-unchanged.
+- k_softmax_rows: 1 row to a third 128-thread block, C = 1 to 1000, logits scaled to 1e4, -inf entries, constant rows.
+- k_sample_stats: S from 1 over 63 / 64 / 65 to ND_STATS_MAXS = 4096, six quantile pairs, uniform / near-constant / heavily tied data,
+  a NaN among the samples (NaN PIW and variance for that (b, c) only).
+- k_report: N = 1 to 2000, C = 1 to 16 (class threads 128..191), 1 to 64 bins, confidences exactly on a bin boundary, empty selections,
+  all-correct and all-wrong votes, out-of-range votes / targets, 64 pairwise different class statistics.
+- nd_image.hip: element counts around the 256-thread block, per-image means from 1 element to 150528, resize to and from size 1, C = 1,
+  crop windows on the bottom / right border, cover squares that overlap, coincide, touch every border or fill the image.
+- k_philox_normal: member 254, trial 65534, class quad 255, the 32-bit wrap of first_image + b and of the batch counter, store mask.
+
+What it does not cover
+- the grid-stride path of the elementwise kernels: it begins above 65535 * 16 blocks (about 2.7e8 elements, more than 1 GB per tensor) and
+  cannot be reached in a test of a few seconds;
+- which side of a bin boundary torchmetrics 0.11.4 puts a confidence on: the oracle restates it (ref_cpu.multiclass_calibration_error_l1,
+  "parity unpinned"); these tests pin kernel = oracle and nothing more;
+- NaN images: adjust_brightness / adjust_contrast of a NaN pixel give 0 where torch.clamp keeps the NaN (pinned below; no call site
+  feeds NaN images).
+
+References are computed inside each test from oracle/ref_cpu.py, plain torch on the CPU, or float64 numpy restating the operation.  Every
+kernel is driven through the small run_* functions below (CPU tensors in, CPU tensors out; caller-owned outputs are 0xFF bytes before the
+call, so an element a kernel leaves unwritten reads as NaN)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as Fn
+
+from oracle import ref_cpu
+from test_gpu_grad_edges import check, poisoned, stream
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+U24 = 2.0 ** -24                 # half an ulp of 1 in fp32
+NAN, INF = float("nan"), float("inf")
+TEMPS = (0.1737, 0.3162, 0.005)
+
+
+def lib():
+    from nested_diffusion_amd import _lib
+    return _lib.load()
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def poisoned_i64(n):
+    return torch.full((n * 8,), 0xFF, dtype=torch.uint8, device=DEV).view(torch.int64)
+
+
+# ---- drivers: CPU tensors in, CPU tensors out --------------------------------------------------------------------------------------
+def run_aggregate(samples, temperature, want_probs=True):
+    S, B, C = samples.shape
+    x = samples.to(DEV).contiguous()
+    prob, vote, probs = poisoned(B, C), poisoned_i64(B), poisoned(S, B, C) if want_probs else None
+    check(lib().nd_aggregate(x.data_ptr(), prob.data_ptr(), vote.data_ptr(), probs.data_ptr() if want_probs else None, S, B, C,
+                             float(temperature), stream()), "nd_aggregate")
+    return prob.cpu(), vote.cpu(), probs.cpu() if want_probs else None
+
+
+def run_softmax(x):
+    from nested_diffusion_amd import ops
+    return ops.softmax_rows(x.to(DEV)).cpu()
+
+
+def run_stats(probs, q_lo, q_hi):
+    S, B, C = probs.shape
+    x = probs.to(DEV).contiguous()
+    piw, var = poisoned(B, C), poisoned(B, C)
+    check(lib().nd_sample_stats(x.data_ptr(), piw.data_ptr(), var.data_ptr(), S, B, C, float(q_lo), float(q_hi), stream()), "nd_sample_stats")
+    return piw.cpu(), var.cpu()
+
+
+def run_report(piw, var, pm, vote, target, temperature, n_bins):
+    """-> fp32 [2 + 4C]: accuracy, ECE, PIW correct / incorrect, variance correct / incorrect per class"""
+    N, C = pm.shape
+    out = poisoned(2 + 4 * C)
+    a = [t.to(DEV).contiguous() for t in (piw, var, pm, vote.to(torch.int64), target.to(torch.int64))]
+    check(lib().nd_report(*[t.data_ptr() for t in a], out.data_ptr(), N, C, float(temperature), int(n_bins), stream()), "nd_report")
+    return out.cpu()
+
+
+def run_add_noise(x, z, std):
+    xd, zd, out = x.to(DEV), z.to(DEV), poisoned(x.numel())
+    check(lib().nd_img_add_noise(xd.data_ptr(), zd.data_ptr(), out.data_ptr(), x.numel(), float(std), stream()), "nd_img_add_noise")
+    return out.cpu()
+
+
+def run_brightness(x, k):
+    xd, out = x.to(DEV), poisoned(x.numel())
+    check(lib().nd_img_brightness(xd.data_ptr(), out.data_ptr(), x.numel(), float(k), stream()), "nd_img_brightness")
+    return out.cpu()
+
+
+def run_contrast(x, k):
+    """x [B, per] -> (out [B, per], mean_ws [B])"""
+    B, per = x.shape
+    xd, out, ws = x.to(DEV).contiguous(), poisoned(B, per), poisoned(B)
+    check(lib().nd_img_contrast(xd.data_ptr(), out.data_ptr(), ws.data_ptr(), B, per, float(k), stream()), "nd_img_contrast")
+    return out.cpu(), ws.cpu()
+
+
+def run_resize(x, Ho, Wo, corners=None, crop=0):
+    B, C, Hi, Wi = x.shape
+    xd, out = x.to(DEV).contiguous(), poisoned(B, C, Ho, Wo)
+    cd = torch.tensor(corners, dtype=torch.int32).reshape(B, 2).to(DEV) if corners is not None else None
+    check(lib().nd_img_resize_bilinear(xd.data_ptr(), out.data_ptr(), B, C, Hi, Wi, Ho, Wo, cd.data_ptr() if cd is not None else None,
+                                       int(crop), stream()), "nd_img_resize_bilinear")
+    return out.cpu()
+
+
+def run_cover(x, rects, side):
+    """rects: [B][n_rects] (top, left); returns the covered copy"""
+    B, C, H, W = x.shape
+    xd = x.to(DEV).contiguous().clone()
+    rd = torch.tensor(rects, dtype=torch.int32).reshape(B, -1, 2).contiguous().to(DEV)
+    check(lib().nd_img_cover(xd.data_ptr(), B, C, H, W, rd.data_ptr(), rd.shape[1], int(side), stream()), "nd_img_cover")
+    return xd.cpu()
+
+
+def run_philox(K, T, B, mc, C, seed, batch_counter=0, first_image=0):
+    out = poisoned(K, T, mc * B, C)
+    check(lib().nd_philox_normal(out.data_ptr(), K, T, B, mc, C, seed, batch_counter, first_image, stream()), "nd_philox_normal")
+    return out.cpu()
+
+
+# ---- 1. aggregation and softmax ------------------------------------------------------------------------------------------------------
+AGG_TOL = 2e-6          # prob / probs against float64: the tolerance of test_gpu_ops.py::test_softmax_and_aggregate_vs_golden
+ROWSUM_TOL = 1e-6       # each probs row sums to 1; derived bound: a fixed-order fp32 sum of C <= 16 terms errs by at most 15 * 2^-24
+                        # relative (9e-7) and the C divisions add at most 2^-24 of the row's mass (measured: 2.6e-7)
+
+
+def agg_oracle(samples, temperature):
+    """(vote, prob32, probs32, prob64, probs64): the reference's functions once in float32 and once on .double() inputs"""
+    S = samples.shape[0]
+    vote = ref_cpu.majority_voting_for_mc_samples([samples[s] for s in range(S)])
+    l32 = [samples[s].clone() for s in range(S)]
+    prob32 = ref_cpu.compute_ensemble_confidence(l32, temperature)           # mutates l32 into the per-sample probabilities
+    l64 = [samples[s].double() for s in range(S)]
+    prob64 = ref_cpu.compute_ensemble_confidence(l64, temperature)
+    return vote, prob32, torch.stack(l32), prob64, torch.stack(l64)
+
+
+def agg_samples(S, B, C, temperature, seed):
+    """y_0 samples around the label value 1 with |logit| = (y - 1)^2 / temperature <= 12: an fp32 logit then carries at most one ulp(8..16)
+    = 9.5e-7 of error, which moves a probability by at most p (1 - p) * 2 * 9.5e-7 <= 5e-7 -- inside AGG_TOL at every temperature.  Half
+    the values lie above 1, so the raw argmax (largest y) and the largest probability (y closest to 1) disagree in many rows."""
+    return 1.0 + (2.0 * torch.rand(S, B, C, generator=gen(seed)) - 1.0) * math.sqrt(12.0 * temperature)
+
+
+AGG_GRID = [(1, 1, 1), (1, 63, 2), (1, 64, 5), (1, 65, 16), (2, 130, 1), (2, 1, 16), (2, 64, 2), (2, 65, 5), (7, 63, 1), (7, 65, 2),
+            (7, 130, 16), (7, 1, 5), (1, 130, 5)]
+
+
+def check_aggregate(samples, temperature):
+    """grid assertions for one launch against the oracle; returns the kernel's outputs"""
+    vote_ref, _, _, prob64, probs64 = agg_oracle(samples, temperature)
+    prob, vote, probs = run_aggregate(samples, temperature)
+    assert torch.equal(vote, vote_ref)
+    e_prob, e_probs = (prob.double() - prob64).abs().max().item(), (probs.double() - probs64).abs().max().item()
+    e_sum = (probs.double().sum(-1) - 1.0).abs().max().item()
+    print(f"aggregate {tuple(samples.shape)} T={temperature}: prob err {e_prob:.2e}, probs err {e_probs:.2e}, row sum err {e_sum:.2e}")
+    assert e_prob <= AGG_TOL and e_probs <= AGG_TOL
+    assert e_sum <= ROWSUM_TOL
+    prob_only, vote_only, _ = run_aggregate(samples, temperature, want_probs=False)
+    assert torch.equal(bits(prob_only), bits(prob)) and torch.equal(vote_only, vote)
+    return prob, vote, probs
+
+
+@pytest.mark.parametrize("S,B,C", AGG_GRID)
+def test_aggregate_grid(S, B, C):
+    assert {s for s, _, _ in AGG_GRID} == {1, 2, 7} and {b for _, b, _ in AGG_GRID} == {1, 63, 64, 65, 130}
+    assert {c for _, _, c in AGG_GRID} == {1, 2, 5, 16}
+    for ti, temperature in enumerate(TEMPS):
+        check_aggregate(agg_samples(S, B, C, temperature, 1000 * S + 10 * B + C + ti), temperature)
+
+
+def test_aggregate_vote_edges():
+    """ties, constant rows, and the raw-argmax / closest-to-1 disagreement in the second 64-thread block"""
+    S, B, C = 6, 65, 5
+    y = agg_samples(S, B, C, 0.1737, 5)
+    # b = 3: a three-way tie (classes 4, 1, 3 twice each): the smallest tied label wins
+    for s, c in enumerate((4, 1, 3, 3, 4, 1)):
+        y[s, 3] = 0.1
+        y[s, 3, c] = 0.9
+    # b = 7: all C entries of every sample equal -> argmax 0 in every sample
+    y[:, 7] = 0.3
+    # b = 64 (first thread of the second block): class 1 has the largest y, class 0 the y closest to 1
+    y[:, 64] = torch.tensor([0.9, 3.0, 0.0, -1.0, 0.2])
+    prob, vote, _ = check_aggregate(y, 0.1737)
+    assert vote[3] == 1 and vote[7] == 0
+    assert vote[64] == 1 and prob[64].argmax() == 0
+    # S = 2 with two different votes is a tie too
+    y2 = torch.tensor([[[0.1, 0.2, 0.9]], [[0.1, 0.9, 0.2]]])
+    assert run_aggregate(y2, 0.1737)[1].tolist() == [1]
+
+
+def test_aggregate_extreme_finite_inputs():
+    """y in {-50, 0.999, 1, 1.001, 60} at temperature 0.005: logits down to -(59^2) / 0.005 = -7e5, probabilities that underflow to exact
+    0 and saturate to exact 1, and rows whose logits differ by 2e-4."""
+    vals = torch.tensor([-50.0, 0.999, 1.0, 1.001, 60.0])
+    pairs = torch.cartesian_prod(vals, vals)                                   # 25 rows, C = 2
+    prob, _, _ = check_aggregate(pairs.reshape(1, 25, 2).contiguous(), 0.005)
+    assert prob[4].tolist() == [1.0, 0.0] and prob[20].tolist() == [0.0, 1.0]          # (-50, 60) and (60, -50): exact
+    assert prob[0].tolist() == [0.5, 0.5]
+    perms = torch.stack([vals.roll(i) for i in range(5)] + [vals.flip(0).roll(i) for i in range(5)])     # 10 rows, C = 5
+    check_aggregate(torch.stack([perms, perms.flip(0)]), 0.005)                # S = 2
+
+
+NONFINITE_ROWS = [[NAN, 0.2, 0.9, 0.4], [0.3, 0.2, NAN, 0.4], [0.3, NAN, 2.0, NAN], [NAN, 1.0, 2.0, 3.0], [0.3, INF, 0.9, 0.4],
+                  [0.3, 0.8, -INF, 0.4], [INF, INF, INF, INF], [0.3, 1e20, 0.9, 0.4], [-INF, -INF, -INF, -INF], [1e20, -1e20, 3e19, 1e20]]
+
+
+def check_nonfinite(y, clean, temperature, poisoned_b):
+    vote_ref, prob32, probs32, prob64, probs64 = agg_oracle(y, temperature)
+    prob, vote, probs = run_aggregate(y, temperature)
+    assert torch.equal(vote, vote_ref), (vote[poisoned_b].tolist(), vote_ref[poisoned_b].tolist())
+    for got, r32, r64 in ((prob, prob32, prob64), (probs, probs32, probs64)):
+        assert torch.equal(got.isnan(), r32.isnan())
+        ok = ~r32.isnan()
+        assert not r64[ok].isnan().any()                                       # the float64 oracle is defined wherever the float32 one is
+        assert (got.double() - r64)[ok].abs().max() <= AGG_TOL
+    # rows without a non-finite value: bit-identical to a launch in which the poisoned rows hold ordinary values
+    prob_c, vote_c, probs_c = run_aggregate(clean, temperature)
+    keep = torch.ones(y.shape[1], dtype=torch.bool)
+    keep[poisoned_b] = False
+    assert keep.sum() >= 100
+    assert torch.equal(bits(prob[keep]), bits(prob_c[keep])) and torch.equal(vote[keep], vote_c[keep])
+    assert torch.equal(bits(probs[:, keep]), bits(probs_c[:, keep]))
+    return prob, vote, probs
+
+
+def test_aggregate_nonfinite_inputs_follow_the_oracle():
+    """NaN at c = 0, at c > 0, twice; +inf, -inf, all +inf, all -inf, 1e20 (whose square overflows).  torch.argmax takes a NaN as the maximum
+    and returns the first one; softmax of a row with a NaN logit, or of all -inf logits, is NaN."""
+    B, C, temperature = 130, 4, 0.1737
+    where = [0, 5, 63, 64, 65, 70, 100, 127, 128, 129][:len(NONFINITE_ROWS)]    # both ends of every block
+    bad = torch.tensor(NONFINITE_ROWS)
+    assert torch.argmax(bad[2:4], dim=1).tolist() == [1, 0]                    # the oracle's rule, as the kernel must have it
+    # S = 1: the vote is the argmax itself
+    clean = agg_samples(1, B, C, temperature, 77)
+    y = clean.clone()
+    y[0, where] = bad
+    _, vote, _ = check_nonfinite(y, clean, temperature, where)
+    assert vote[where[:4]].tolist() == [0, 2, 1, 0]
+    # S = 3, poisoned in the middle sample only: the NaN reaches the mean, the other samples' probabilities stay finite
+    clean = agg_samples(3, B, C, temperature, 78)
+    y = clean.clone()
+    y[1, where] = bad
+    prob, _, probs = check_nonfinite(y, clean, temperature, where)
+    assert prob[where[0]].isnan().all() and not probs[0].isnan().any() and not probs[2].isnan().any()
+
+
+SOFTMAX_TOL = 1e-6      # against float64 torch.softmax: the tolerance of test_gpu_ops.py::test_softmax_and_aggregate_vs_golden
+
+
+@pytest.mark.parametrize("C", [1, 2, 16, 1000])
+def test_softmax_rows_edges(C):
+    worst = 0.0
+    for rows in (1, 127, 128, 129, 300):
+        for scale in (1.0, 30.0, 1e4):
+            x = torch.randn(rows, C, generator=gen(rows * 7 + C)) * scale
+            x[rows - 1] = 3.25 * scale                                         # a row of equal values (the last row of the last block)
+            if C > 1 and rows > 1:
+                x[0, ::2] = -INF                                               # -inf entries beside finite ones
+            got = run_softmax(x)
+            ref = torch.softmax(x.double(), dim=1)
+            worst = max(worst, (got.double() - ref).abs().max().item())
+            assert (got[rows - 1].double() - 1.0 / C).abs().max() <= SOFTMAX_TOL
+            if C > 1 and rows > 1:
+                assert (got[0, ::2] == 0).all()
+    print(f"softmax C={C}: worst err {worst:.2e}")
+    assert worst <= SOFTMAX_TOL
+
+
+# ---- 2. sample_stats -----------------------------------------------------------------------------------------------------------------
+QUANTILES = [(0.025, 0.975), (0.0, 1.0), (0.5, 0.5), (0.3, 0.3000001), (0.0, 0.0), (1.0, 1.0)]
+PIW_TOL = 1e-6          # absolute, against float64 numpy.quantile: the tolerance of test_gpu_ops.py::test_sample_stats_and_report_vs_golden_and_oracle
+VAR_ABS, VAR_REL = 1e-7, 1e-5
+# |var - var64| <= VAR_ABS + VAR_REL * var64.  A CPU emulation of the kernel's summation (64 lane-strided partials, xor butterfly, two passes)
+# measured 5.5e-8 absolute and 6e-7 relative on these inputs.  Worst figures measured on an MI355X over this whole grid:
+# PIW 2.4e-7 absolute; variance 4.3e-8 absolute (at S = 4096) and 4.6e-7 relative where var > 1e-3.
+
+
+def stats_data(kind, S, B, C, seed):
+    g = gen(seed)
+    if kind == "uniform":
+        return torch.rand(S, B, C, generator=g)
+    if kind == "near_constant":
+        return 0.999 + 1e-4 * torch.randn(S, B, C, generator=g)
+    x = torch.round(torch.rand(S, B, C, generator=g) * 4) / 4                 # heavily tied: quarters
+    x[:, 0, 0] = 0.5                                                           # a (b, c) whose values are all equal
+    return x
+
+
+def stats_reference(x, q_lo, q_hi):
+    """float64 numpy.quantile (linear) at the float32 values of the quantiles; float64 var(ddof=1) of the same float32 inputs"""
+    x64 = x.double().numpy()
+    lo = np.quantile(x64, float(np.float32(q_lo)), axis=0)
+    hi = np.quantile(x64, float(np.float32(q_hi)), axis=0)
+    var = x64.var(axis=0, ddof=1) if x.shape[0] > 1 else np.full(x64.shape[1:], np.nan)
+    return hi - lo, var
+
+
+STATS_WORST = {"piw": 0.0, "var_abs": 0.0, "var_rel": 0.0}
+
+
+@pytest.mark.parametrize("S,B,C", [(S, 3, 2) for S in (1, 2, 3, 41, 63, 64, 65, 128, 1000, 4096)] + [(41, 70, 16)])
+def test_sample_stats_grid(S, B, C):
+    for ki, kind in enumerate(("uniform", "near_constant", "tied")):
+        x = stats_data(kind, S, B, C, 31 * S + ki)
+        for q_lo, q_hi in QUANTILES:
+            piw, var = run_stats(x, q_lo, q_hi)
+            piw_ref, var_ref = stats_reference(x, q_lo, q_hi)
+            e_piw = np.abs(piw.double().numpy() - piw_ref).max()
+            STATS_WORST["piw"] = max(STATS_WORST["piw"], e_piw)
+            assert e_piw <= PIW_TOL, (kind, q_lo, q_hi, e_piw)
+            if q_lo == q_hi:
+                assert (piw == 0).all()
+            if S == 1:
+                assert var.isnan().all() and (piw == 0).all()                  # torch.var of one value is NaN; its quantiles coincide
+                continue
+            e_var = np.abs(var.double().numpy() - var_ref)
+            STATS_WORST["var_abs"] = max(STATS_WORST["var_abs"], e_var.max())
+            STATS_WORST["var_rel"] = max(STATS_WORST["var_rel"], (e_var / np.maximum(var_ref, 1e-30))[var_ref > 1e-3].max(initial=0.0))
+            assert (e_var <= VAR_ABS + VAR_REL * var_ref).all(), (kind, e_var.max())
+            if kind == "tied":
+                assert var[0, 0] == 0 and piw[0, 0] == 0
+    print(f"sample_stats S={S} B={B} C={C}: worst so far piw {STATS_WORST['piw']:.1e} abs; var {STATS_WORST['var_abs']:.1e} abs, "
+          f"{STATS_WORST['var_rel']:.1e} relative (where var > 1e-3)")
+
+
+@pytest.mark.parametrize("S", [1, 2, 41, 65, 130])
+def test_sample_stats_nan_among_the_samples(S):
+    """A NaN has no rank, so the kernel cannot pick order statistics: that (b, c) gets NaN PIW and variance, as torch.quantile and var give;
+    every other (b, c) of the launch is bit-identical to a launch without the NaN.  (The value an unfixed kernel returned came from
+    shared memory nobody wrote, so only isnan is asserted.)"""
+    B, C = 3, 2
+    clean = stats_data("uniform", S, B, C, 900 + S)
+    for pos in sorted({0, S // 2, S - 1}):
+        x = clean.clone()
+        x[pos, 1, 0] = NAN
+        assert torch.quantile(x[:, 1, 0], 0.5).isnan() and (S == 1 or x[:, 1, 0].var().isnan())
+        for q_lo, q_hi in QUANTILES[:3]:
+            piw, var = run_stats(x, q_lo, q_hi)
+            piw_c, var_c = run_stats(clean, q_lo, q_hi)
+            assert piw[1, 0].isnan() and var[1, 0].isnan(), (pos, q_lo, q_hi, piw[1, 0].item(), var[1, 0].item())
+            keep = torch.ones(B, C, dtype=torch.bool)
+            keep[1, 0] = False
+            assert torch.equal(bits(piw[keep]), bits(piw_c[keep])) and torch.equal(bits(var[keep]), bits(var_c[keep]))
+
+
+# ---- 3. report -----------------------------------------------------------------------------------------------------------------------
+BINS = (1, 3, 7, 10, 15, 64)
+REPORT_TEMPS = (0.1737, 0.005)
+ACC_TOL, REPORT_TOL = 1e-7, 2e-6        # the tolerances of test_gpu_ops.py::test_sample_stats_and_report_vs_golden_and_oracle
+CLEARANCE = 1e-5                        # an ordinary row's confidence keeps this distance from every bin boundary: the device's expf may differ
+                                        # from the host's in the last place (about 1e-7 here), which must not move a row to another bin
+
+
+def class_means_reference(piw, var, vote, target, C):
+    """compute_mean_piws_for_class / calculate_variances restated in float64 directly from the per-image piw and var arrays (rather
+    than feeding the oracle per-sample lists with that spread): mean PIW of the voted class over the correct / incorrect votes for c (NaN
+    when none), mean variance (0 when none).  Votes outside [0, C) select no class.
+    -> (the 4C means, the 4C derived bounds count * 2^-24 * mean of the selected values: the kernel adds the `count` selected fp32 values in
+    a fixed order, each addition within 2^-24 of a running sum that never exceeds the total, and divides once)"""
+    out, bound = np.zeros((4, C)), np.zeros((4, C))
+    p, v, mv, gt = piw.double().numpy(), var.double().numpy(), vote.numpy(), target.numpy()
+    for c in range(C):
+        for wrong in (0, 1):
+            sel = (mv == c) & ((mv != gt) if wrong else (mv == gt))
+            out[wrong, c] = p[sel, c].mean() if sel.any() else np.nan
+            out[2 + wrong, c] = v[sel, c].mean() if sel.any() else 0.0
+            if sel.any():
+                bound[wrong, c], bound[2 + wrong, c] = sel.sum() * U24 * p[sel, c].mean(), sel.sum() * U24 * v[sel, c].mean()
+    return out.reshape(-1), bound.reshape(-1)
+
+
+def boundary_distance(conf, bins=BINS):
+    """smallest distance of each confidence to an interior boundary of linspace(0, 1, n + 1) for every n in bins.  The ends do not count:
+    a confidence lies in [1 / C, 1], 1.0 is the closed end of the last bin and nothing lies beyond it, so a last-place difference near 0
+    or 1 cannot move a row to another bin (at temperature 0.005 most confidences are within 1e-5 of 1)."""
+    d = torch.full_like(conf, 1.0)
+    for n in bins:
+        if n > 1:
+            d = torch.minimum(d, (conf[:, None] - torch.linspace(0, 1, n + 1)[None, 1:-1]).abs().min(dim=1).values)
+    return d
+
+
+def ordinary_rows(N, C, seed):
+    """probability rows whose oracle confidence, at both temperatures, is at least CLEARANCE from every bin boundary (redrawn until so)"""
+    g = gen(seed)
+    pm = torch.softmax(torch.randn(N, C, generator=g) * 2.0, dim=1)
+    for _ in range(50):
+        bad = torch.zeros(N, dtype=torch.bool)
+        for t in REPORT_TEMPS:
+            bad |= boundary_distance(ref_cpu.convert_to_prob(pm, t).max(dim=1).values) < CLEARANCE
+        if C == 1 or not bad.any():                                            # C = 1: exp(0) / exp(0) is exactly 1 on host and device alike
+            return pm
+        pm[bad] = torch.softmax(torch.randn(int(bad.sum()), C, generator=g) * 2.0, dim=1)
+    raise AssertionError(f"{int(bad.sum())} of {N} rows still within {CLEARANCE} of a bin boundary after 50 redraws")
+
+
+def assert_clear_of_boundaries(pm, temperature, bins, exempt=None):
+    conf = ref_cpu.convert_to_prob(pm, temperature).max(dim=1).values
+    d = boundary_distance(conf, bins)
+    if exempt is not None:
+        d = d[~exempt]
+    assert (d >= CLEARANCE).all()
+
+
+def check_report(piw, var, pm, vote, target, temperature, n_bins, derived=False):
+    """One launch against the references.  derived=False: accuracy at ACC_TOL, everything else at REPORT_TOL (ECE: the float32 oracle).
+    derived=True (N = 2000, where fixed-order fp32 sums of N values may err by more than REPORT_TOL): every quantity against its own bound,
+      class mean: count * 2^-24 * mean of the selected values, against the float64 restatement (class_means_reference);
+      ECE: N * 2^-24 * mean(conf), against the oracle fed the same float32 probabilities as float64, so that its own sums are exact and
+        nothing has to be doubled.  Per bin the kernel adds count_k confidences (error <= count_k * 2^-24 * csum_k) and the ECE is
+        sum_k |asum_k - csum_k| / N, so the error is at most 2^-24 * sum_k csum_k = N * 2^-24 * mean(conf), reached when one bin holds every
+        row; the device's expf moves a confidence by about 1e-7, three orders below that.
+    -> (outputs, worst error / asserted tolerance, number of asserted tolerances above REPORT_TOL)"""
+    N, C = pm.shape
+    got = run_report(piw, var, pm, vote, target, temperature, n_bins).double().numpy()
+    assert abs(got[0] - float(ref_cpu.compute_accuracy(vote, target))) <= ACC_TOL
+    probs = ref_cpu.convert_to_prob(pm, temperature)
+    ref, bound = class_means_reference(piw, var, vote, target, C)
+    if derived:
+        ece = float(ref_cpu.multiclass_calibration_error_l1(probs.double(), target, n_bins))
+        ece_tol, tol = N * U24 * float(probs.max(dim=1).values.double().mean()), bound
+    else:
+        ece = float(ref_cpu.multiclass_calibration_error_l1(probs, target, n_bins))
+        ece_tol, tol = REPORT_TOL, np.full_like(bound, REPORT_TOL)
+    assert abs(got[1] - ece) <= ece_tol, (got[1], ece, ece_tol)
+    assert np.array_equal(np.isnan(got[2:]), np.isnan(ref)), (got[2:], ref)
+    err = np.nan_to_num(np.abs(got[2:] - ref), nan=0.0)
+    assert (err <= tol).all(), (err, tol)
+    ratio = max(abs(got[1] - ece) / ece_tol, (err[tol > 0] / tol[tol > 0]).max(initial=0.0))
+    return got, ratio, int(ece_tol > REPORT_TOL) + int((tol > REPORT_TOL).sum())
+
+
+@pytest.mark.parametrize("N", [1, 5, 257, 2000])
+@pytest.mark.parametrize("C", [1, 2, 3, 16])
+def test_report_grid(N, C):
+    g = gen(17 * N + C)
+    pm = ordinary_rows(N, C, 17 * N + C)
+    piw, var = torch.rand(N, C, generator=g), 0.1 * torch.rand(N, C, generator=g)
+    vote, target = torch.randint(0, C, (N,), generator=g), torch.randint(0, C, (N,), generator=g)
+    # Up to N = 257 everything is asserted at the existing 2e-6.  At N = 2000 each quantity is asserted against its own derived bound
+    # (check_report).  Of those, the ECE's (N * 2^-24 * mean(conf), about 1e-4) EXCEEDS 2e-6, and so does a class mean's whenever
+    # count * mean > 33.5: from about 70 selected PIW values (mean 0.5) or 700 selected variances (mean 0.05) -- at C = 1 both kinds, at
+    # C = 2 and 3 the PIW means, at C = 16 the PIW means over the incorrect votes.  The other bounds are tighter than 2e-6 (down to 2e-8) and
+    # are asserted as they are.  The number of bounds above 2e-6 and the worst error / bound are printed.
+    derived = N == 2000
+    worst, loose = 0.0, 0
+    for temperature in REPORT_TEMPS:
+        if C > 1:
+            assert_clear_of_boundaries(pm, temperature, BINS)
+        for n_bins in BINS:
+            _, ratio, n_loose = check_report(piw, var, pm, vote, target, temperature, n_bins, derived)
+            worst, loose = max(worst, ratio), max(loose, n_loose)
+    print(f"report N={N} C={C}: worst error / asserted tolerance {worst:.3f}; {loose} of {1 + 4 * C} tolerances above {REPORT_TOL}"
+          f" ({'derived bounds' if derived else 'all ' + str(REPORT_TOL)})")
+
+
+def ece_oracle(probs, target, n_bins):
+    return float(ref_cpu.multiclass_calibration_error_l1(probs, target, n_bins))
+
+
+@pytest.mark.parametrize("C,n_bins,temperature,row", [(2, 10, 0.1737, [0.5, 0.5]), (4, 4, 0.1737, [0.25] * 4), (2, 10, 0.005, [1.0, 0.0]),
+                                                      (2, 64, 0.005, [1.0, 0.0])])
+def test_report_confidence_exactly_on_a_bin_boundary(C, n_bins, temperature, row):
+    """Equal entries give confidence exactly 1 / C (0.5 = linspace(0, 1, 11)[5], 0.25 = linspace(0, 1, 5)[1]); [1, 0] at temperature 0.005
+    gives exactly 1.0, the closed end of the last bin.  A bin is (lo, hi]: the boundary rows belong to the lower bin."""
+    n_edge, n_ord = 12, 28
+    N = n_edge + n_ord
+    pm = ordinary_rows(n_ord, C, 400 + C + n_bins)
+    want = 1.0 if row[0] == 1.0 else 1.0 / C
+    if want < 1.0:      # eight ordinary rows just above 1 / C, so that the bin above the boundary is populated
+        tilt = torch.tensor([1.0] + [-1.0 / (C - 1)] * (C - 1))
+        pm[:8] = torch.tensor(row) + (0.01 + 0.02 * torch.rand(8, 1, generator=gen(C))) * tilt
+    pm = torch.cat([pm[:10], torch.tensor([row] * n_edge), pm[10:]])
+    edge = torch.zeros(N, dtype=torch.bool)
+    edge[10:10 + n_edge] = True
+    probs = ref_cpu.convert_to_prob(pm, temperature)
+    conf, pred = probs.max(dim=1)
+    assert (conf[edge] == want).all() and float(torch.linspace(0, 1, n_bins + 1)[round(want * n_bins)]) == want
+    assert_clear_of_boundaries(pm, temperature, (n_bins,), exempt=edge)
+    # boundary rows all correct and ordinary rows all wrong (all wrong / all correct for the 1.0 rows): moving the boundary rows then
+    # changes both bins' |accuracy - confidence|
+    target = torch.where(edge == (want < 1.0), pred, (pred + 1) % C)
+    ece = ece_oracle(probs, target, n_bins)
+    if want < 1.0:      # the same rows one ulp higher fall into the next bin
+        moved = probs.clone()
+        moved[edge, 0] = torch.nextafter(torch.tensor(want), torch.tensor(1.0))
+        assert torch.equal(moved.max(dim=1).indices, pred)
+        ece_moved = ece_oracle(moved, target, n_bins)
+    else:               # 1.0 outside the last bin would drop the rows from every bin
+        ece_moved = ece_oracle(probs[~edge], target[~edge], n_bins) * n_ord / N
+    assert abs(ece - ece_moved) > 1e-3, (ece, ece_moved)                       # so a kernel with the boundary on the other side fails below
+    g = gen(5)
+    piw, var, vote = torch.rand(N, C, generator=g), torch.rand(N, C, generator=g), torch.randint(0, C, (N,), generator=g)
+    got, _, _ = check_report(piw, var, pm, vote, target, temperature, n_bins)
+    assert abs(got[1] - ece_moved) > 5e-4
+
+
+def test_report_selections():
+    g = gen(23)
+    # classes nobody voted for: NaN PIW, 0 variance
+    N, C = 40, 3
+    pm = ordinary_rows(N, C, 61)
+    piw, var = torch.rand(N, C, generator=g), torch.rand(N, C, generator=g)
+    vote, target = torch.randint(0, 2, (N,), generator=g) * 2, torch.randint(0, C, (N,), generator=g)
+    assert_clear_of_boundaries(pm, 0.1737, (10,))
+    got, _, _ = check_report(piw, var, pm, vote, target, 0.1737, 10)
+    assert np.isnan(got[2 + 1]) and np.isnan(got[2 + C + 1]) and got[2 + 2 * C + 1] == 0 and got[2 + 3 * C + 1] == 0
+    # every vote correct, every vote wrong
+    vote = torch.randint(0, C, (N,), generator=g)
+    got, _, _ = check_report(piw, var, pm, vote, vote.clone(), 0.1737, 10)
+    assert got[0] == 1.0 and np.isnan(got[2 + C:2 + 2 * C]).all() and (got[2 + 3 * C:] == 0).all()
+    got, _, _ = check_report(piw, var, pm, vote, (vote + 1) % C, 0.1737, 10)
+    assert got[0] == 0.0 and np.isnan(got[2:2 + C]).all() and (got[2 + 2 * C:2 + 3 * C] == 0).all()
+    # votes and targets >= C: such a vote selects no class, such a target makes the vote for c an incorrect one
+    vote2, target2 = vote.clone(), vote.clone()
+    vote2[::5] = C + 1
+    target2[1::5] = C
+    target2[0] = C + 1                                                         # equal to its (out-of-range) vote: counts for the accuracy only
+    check_report(piw, var, pm, vote2, target2, 0.1737, 10)
+    # C = 16: the 64 class statistics (threads 128..191) all differ pairwise, so a thread-to-slot mix-up cannot cancel
+    N, C = 257, 16
+    pm = ordinary_rows(N, C, 62)
+    i = torch.arange(N)
+    vote = i % C
+    wrong = (i // C) % 2
+    target = torch.where(wrong == 0, vote, (vote + 1 + i // 32) % C)
+    level = (1 + 16 * wrong[:, None] + torch.arange(C)[None, :]) / 70.0        # statistic (kind, c) sits near (1 + 16 kind + c) / 70
+    piw = level + 2e-3 * torch.rand(N, C, generator=g)
+    var = level + 32 / 70.0 + 2e-3 * torch.rand(N, C, generator=g)
+    ref, _ = class_means_reference(piw, var, vote, target, C)
+    assert not np.isnan(ref).any() and np.diff(np.sort(ref)).min() > 1e-3
+    assert_clear_of_boundaries(pm, 0.1737, (64,))
+    check_report(piw, var, pm, vote, target, 0.1737, 64)
+
+
+# ---- 4. image kernels ----------------------------------------------------------------------------------------------------------------
+ELEMENT_COUNTS = (1, 255, 256, 257, 1000003)
+
+
+@pytest.mark.parametrize("n", ELEMENT_COUNTS)
+def test_add_noise_and_brightness_bit_exact(n):
+    """one rounding per operation (contraction off): bit-identical to float32 torch"""
+    g = gen(n)
+    x = torch.rand(n, generator=g) * 2.0 - 0.5                                 # inputs outside [0, 1] too
+    z = torch.randn(n, generator=g)
+    for std in (0.3, 0.0, 1e-3):
+        assert torch.equal(bits(run_add_noise(x, z, std)), bits(ref_cpu.add_noise(x, std, z)))
+    for k in (0.4, -0.3, 0.0, -0.0, 1.5):
+        assert torch.equal(bits(run_brightness(x, k)), bits(ref_cpu.adjust_brightness(x, k))), k
+
+
+def test_brightness_and_contrast_of_a_nan_pixel():
+    """Difference from the oracle, pinned: torch.clamp keeps a NaN, the kernels' fminf(fmaxf(v, 0), 1) returns the non-NaN operand, so a NaN
+    pixel becomes 0.  No call site feeds NaN images (they come from the loader's [0, 1] tensors), so the kernels stay as they are.
+    add_noise has no clamp and propagates the NaN as torch does."""
+    x = torch.tensor([0.25, NAN, 0.75, 2.0, -1.0])
+    assert ref_cpu.adjust_brightness(x, 0.1)[1].isnan()
+    got = run_brightness(x, 0.1)
+    assert got[1] == 0 and torch.equal(got[[0, 2, 3, 4]], ref_cpu.adjust_brightness(x, 0.1)[[0, 2, 3, 4]])
+    assert run_add_noise(x, torch.ones(5), 0.5)[1].isnan()
+    out, mean = run_contrast(x.reshape(1, 5), 1.7)                             # the image's mean is NaN: every pixel of that image becomes 0
+    assert mean.isnan().all() and (out == 0).all()
+
+
+@pytest.mark.parametrize("per", [1, 5, 63, 64, 65, 1023, 1024, 1025, 150528])
+@pytest.mark.parametrize("B", [1, 3])
+def test_contrast_mean_and_output(per, B):
+    g = gen(per + B)
+    x = torch.rand(B, per, generator=g) * 0.5 + 0.2 * torch.arange(B, dtype=torch.float32)[:, None]      # a different mean per image
+    x64 = x.double()
+    # derived: each of the 1024 strided partials is a sum of ceil(per / 1024) terms, then six shuffle adds and sixteen wave partials, each
+    # addition within 2^-24 of a running sum that never exceeds the sum of |x|
+    bound = (math.ceil(per / 1024) + 22) * U24 * x64.abs().mean(dim=1)
+    for k in (0.0, 0.4, 1.0, 1.7):
+        out, mean = run_contrast(x, k)
+        err = (mean.double() - x64.mean(dim=1)).abs()
+        assert (err <= bound).all(), (err, bound)
+        m = mean[:, None]
+        ref = torch.clamp(m + (x - m) * k, 0, 1)                               # float32, one rounding per operation, the kernel's own mean
+        assert torch.equal(bits(out), bits(ref)), k
+    print(f"contrast per={per} B={B}: mean err / bound {float((err / bound).max()):.2f}")
+
+
+RESIZE_TOL = 3e-7       # the tolerance of test_gpu_ops.py::test_perturbation_ops_vs_reference_goldens
+RESIZE_CASES = [((1, 1), (5, 7)), ((7, 5), (1, 1)), ((24, 20), (24, 20)), ((7, 9), (224, 224)), ((224, 224), (74, 74)),
+                ((224, 224), (75, 74)), ((2, 3), (3, 2)),
+                ((201, 201), (224, 224))]      # a crop of 10 % resized back: source coordinates near 200, where rounding the product before
+                                               # the subtraction moves a weight by 1.5e-5 and the result by up to 4e-6
+
+
+def resize_axis(n_in, n_out):
+    """source indices and weights of one axis in float32, exactly as torch computes them (align_corners=False):
+    scale = float(in) / out, src = max(scale * (dst + 0.5) - 0.5, 0) with the multiply-add fused (one rounding: the float64 expression
+    below is exact before it is rounded to float32), neighbours clamped.  CPU F.interpolate agrees with this form because torch's x86
+    kernels are built with FMA (AVX2 / AVX-512) and contract the expression; on a host whose torch rounds the product first, the (7, 9) ->
+    (224, 224) case would differ from F.interpolate by 4.4e-7 while still matching this restatement."""
+    scale = np.float64(np.float32(n_in) / np.float32(n_out))
+    dst = np.arange(n_out, dtype=np.float64)
+    src = np.maximum((scale * (dst + 0.5) - 0.5).astype(np.float32), np.float32(0.0))
+    i0 = np.minimum(src.astype(np.int64), n_in - 1)
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = (src - i0.astype(np.float32)).astype(np.float32)
+    l0 = (np.float32(1.0) - l1).astype(np.float32)
+    return i0, i1, l0.astype(np.float64), l1.astype(np.float64)
+
+
+def resize_reference(x, Ho, Wo):
+    """float64 blend over float32 indices and weights; x [..., Hi, Wi]"""
+    x64 = x.double().numpy()
+    y0, y1, hy, ly = resize_axis(x.shape[-2], Ho)
+    x0, x1, hx, lx = resize_axis(x.shape[-1], Wo)
+    top = hx * x64[..., y0[:, None], x0[None, :]] + lx * x64[..., y0[:, None], x1[None, :]]
+    bot = hx * x64[..., y1[:, None], x0[None, :]] + lx * x64[..., y1[:, None], x1[None, :]]
+    return torch.from_numpy(hy[:, None] * top + ly[:, None] * bot)
+
+
+@pytest.mark.parametrize("src,dst", RESIZE_CASES)
+def test_resize_bilinear_edges(src, dst):
+    (Hi, Wi), (Ho, Wo) = src, dst
+    for B, C in ((1, 1), (3, 3), (1, 3), (3, 1)):
+        x = torch.rand(B, C, Hi, Wi, generator=gen(Hi * Wo + B + C))
+        got = run_resize(x, Ho, Wo).double()
+        assert (got - resize_reference(x, Ho, Wo)).abs().max() <= RESIZE_TOL
+        assert (got - Fn.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=False).double()).abs().max() <= RESIZE_TOL
+        if src == dst:
+            assert torch.equal(got.float(), x)                                 # identity: weight 0 on the neighbour
+
+
+@pytest.mark.parametrize("s", [1, 15, 17])
+def test_resize_crop_windows_on_the_borders(s):
+    """per-image windows at the top-left, bottom-right and top-right corners of a non-square source (C = 3, B = 3: the image of a plane is
+    nc / C), resized back to the source size as random_crop_and_resize does"""
+    B, C, Hi, Wi = 3, 3, 17, 23
+    x = torch.rand(B, C, Hi, Wi, generator=gen(s))
+    corners = [(0, 0), (Hi - s, Wi - s), (0, Wi - s)]
+    got = run_resize(x, Hi, Wi, corners, s)
+    ref = ref_cpu.crop_and_resize(x, corners, s)
+    assert (got - ref).abs().max() <= RESIZE_TOL
+    windows = torch.stack([x[b, :, t:t + s, l:l + s] for b, (t, l) in enumerate(corners)])
+    assert (got.double() - resize_reference(windows, Hi, Wi)).abs().max() <= RESIZE_TOL
+
+
+def cover_rects(H, W, side):
+    """three images: overlapping squares, squares flush with every border, identical squares"""
+    th, tw = H - side, W - side                                                # largest top / left
+    return [[(0, 0), (min(side // 2 + 1, th), min(side // 2, tw)), (min(side // 2, th), min(1, tw))],
+            [(0, 0), (th, tw), (0, tw)] if (th, tw) != (0, 0) else [(0, 0)] * 3,
+            [(th // 2, tw // 2)] * 3]
+
+
+@pytest.mark.parametrize("H,W,side", [(9, 9, 0), (9, 9, 1), (9, 9, 5), (9, 9, 9), (6, 10, 6), (10, 6, 6)])
+def test_cover_edges(H, W, side):
+    rects3 = cover_rects(H, W, side)
+    rects3[1] = rects3[1] + [(H - side, 0)]                                    # the fourth border corner, used when n_rects allows
+    for C in (1, 3):
+        for n_rects in (1, 3):
+            rects = [r[:n_rects] for r in rects3]
+            if n_rects == 3:
+                rects[1] = [rects3[1][1], rects3[1][2], rects3[1][3]]          # bottom-right, top-right, bottom-left
+            x = torch.rand(3, C, H, W, generator=gen(H + side + C)) + 0.1      # no zeros in the input
+            got = run_cover(x, rects, side)
+            ref = ref_cpu.cover_regions(x, rects, side)
+            assert torch.equal(bits(got), bits(ref))
+            covered = torch.zeros(3, 1, H, W, dtype=torch.bool)
+            for b, rs in enumerate(rects):
+                for t, l in rs:
+                    covered[b, :, t:t + side, l:l + side] = True
+            covered = covered.expand(3, C, H, W)
+            assert (got[covered] == 0).all() and torch.equal(bits(got[~covered]), bits(x[~covered]))
+            assert int(covered.sum()) > 0 or side == 0
+
+
+# ---- 5. noise ------------------------------------------------------------------------------------------------------------------------
+PHILOX_TOL = 5e-6       # against ref_cpu.philox_normal (float64 Box-Muller): the tolerance of tests/test_gpu_batch.py
+Z_MAX = math.sqrt(64 * math.log(2)) + 1e-5      # u1 >= 2^-32, so r = sqrt(-2 ln u1) <= sqrt(64 ln 2)
+SEED = 0x9E3779B97F4A7C15
+PHILOX_CASES = [dict(K=255, T=1, B=1, mc=1, C=1), dict(K=1, T=1, B=1, mc=65535, C=1), dict(K=1, T=2, B=3, mc=1, C=1024),
+                dict(K=2, T=3, B=5, mc=2, C=7), dict(K=1, T=1, B=2, mc=1, C=4), dict(K=1, T=1, B=2, mc=1, C=5),
+                dict(K=2, T=1, B=4, mc=2, C=3, first_image=0xFFFFFFFE), dict(K=2, T=2, B=3, mc=2, C=6, batch_counter=0xFFFFFFFF)]
+
+
+def check_philox(z, **kw):
+    assert torch.isfinite(z).all()                                             # also: every element was written (the buffer was all NaN)
+    assert z.abs().max() <= Z_MAX
+    ref = ref_cpu.philox_normal(kw["K"], kw["T"], kw["B"], kw["mc"], kw["C"], SEED, kw.get("batch_counter", 0), kw.get("first_image", 0))
+    assert z.shape == ref.shape
+    assert (z - ref).abs().max() <= PHILOX_TOL
+
+
+@pytest.mark.parametrize("case", PHILOX_CASES, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+def test_philox_normal_field_limits(case):
+    """the smallest tensors that reach member 254, trial 65534, class quad 255, and the 32-bit wraps of the image word and batch counter"""
+    z = run_philox(case["K"], case["T"], case["B"], case["mc"], case["C"], SEED, case.get("batch_counter", 0), case.get("first_image", 0))
+    check_philox(z, **case)
+
+
+def test_philox_normal_store_mask_member_prefix_and_shards():
+    K, T, B, mc = 2, 3, 5, 2
+    z5, z8 = run_philox(K, T, B, mc, 5, SEED), run_philox(K, T, B, mc, 8, SEED)
+    check_philox(z5, K=K, T=T, B=B, mc=mc, C=5)
+    check_philox(z8, K=K, T=T, B=B, mc=mc, C=8)
+    assert torch.equal(bits(z5), bits(z8[..., :5]))                            # same counters, only the store mask differs
+    z3 = run_philox(3, T, B, mc, 5, SEED)
+    assert torch.equal(bits(z3[:2]), bits(z5))                                 # a member's draws do not depend on the ensemble size
+    # shard independence across the wrap: images 0xFFFFFFFF and 0 of a 4-image batch starting at 0xFFFFFFFE
+    T, mc, C = 2, 3, 6
+    z4 = run_philox(K, T, 4, mc, C, SEED, 7, 0xFFFFFFFE).reshape(K, T, mc, 4, C)
+    z2 = run_philox(K, T, 2, mc, C, SEED, 7, 0xFFFFFFFF).reshape(K, T, mc, 2, C)
+    check_philox(z4.reshape(K, T, mc * 4, C), K=K, T=T, B=4, mc=mc, C=C, batch_counter=7, first_image=0xFFFFFFFE)
+    assert torch.equal(bits(z4[:, :, :, 1:3]), bits(z2))
