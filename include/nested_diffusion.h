@@ -184,7 +184,9 @@ int nd_loop_form(nd_handle h);
 int nd_persist_status(nd_handle h, int reset);
 
 /* Copy of an internal per-member activation (tests / debugging), converted from the packed layout to
- * row-major: which = 0 xe [rows<=B, F], 1 h1 [rows<=M, F], 2 h2 [rows<=M, F] -> dst_dev [rows, F]. */
+ * row-major: which = 0 xe [rows<=B, F], 1 h1 [rows<=M, F], 2 h2 [rows<=M, F] -> dst_dev [rows, F];
+ * which = 3 e0, 4 e1 (the encoder's two hidden activations of the last nd_encode) [rows<=B, hidden_dim] -> dst_dev [rows, hidden_dim].
+ * Arguments are checked before the handle's state: ND_ERR_ARG for an unknown `which` or too many rows, also on an unbound handle. */
 int nd_member_buffer(nd_handle h, int member, int which, float *dst_dev, int rows, void *stream);
 
 /* ---- standalone operators (mapping network + unit tests) ---------------------------------- */

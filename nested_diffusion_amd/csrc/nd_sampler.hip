@@ -805,23 +805,26 @@ static int encode_impl(nd_handle h, int m0, int nm, const float* x_dev, int B, v
 }
 
 extern "C" int nd_member_buffer(nd_handle h, int k, int which, float* dst_dev, int rows, void* stream) {
-    if (!h || !h->ws || !dst_dev) return nd_set_err(ND_ERR_ARG, "bad argument");
+    // arguments first (host-only callers get the same answers on an unbound handle), then the state
+    if (!h || !dst_dev) return nd_set_err(ND_ERR_ARG, "bad argument");
     if (k < 0 || k >= h->cfg.n_members) return nd_set_err(ND_ERR_ARG, "member out of range");
+    if (which < 0 || which > 4) return nd_set_err(ND_ERR_ARG, "which=%d unknown", which);
     if (rows < 1 || rows > h->cfg.max_rows) return nd_set_err(ND_ERR_ARG, "rows out of range");
+    const bool enc = which == 0 || which >= 3;       // xe, e0, e1: written by nd_encode, one row per image
+    if (enc && rows > h->cfg.max_batch) return nd_set_err(ND_ERR_ARG, "%s holds at most max_batch rows", which == 0 ? "xe" : which == 3 ? "e0" : "e1");
+    if (!h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");
     MemberHost& m = h->members[k];
-    const float* src = which == 0 ? m.xe : which == 1 ? m.h1 : which == 2 ? m.h2 : nullptr;
-    if (!src) return nd_set_err(ND_ERR_ARG, "which=%d unknown", which);
-    if (which == 0 && rows > h->cfg.max_batch) return nd_set_err(ND_ERR_ARG, "xe holds at most max_batch rows");
-    const int F = h->cfg.feature_dim;
+    const float* src = which == 0 ? m.xe : which == 1 ? m.h1 : which == 2 ? m.h2 : which == 3 ? m.e0 : m.e1;
+    const int W = which >= 3 ? h->cfg.hidden_dim : h->cfg.feature_dim;      // e0 / e1 are hidden_dim wide
     // above 128 rows the step blocks of an fp32 handle run on frag32b3 images of h1 / h2 (bf16 matrix pipe): the live copies are
     // whichever the LAST launch over this member wrote (MemberHost::h_split), not what `rows` would pick
-    if (which != 0 && m.h_split) return nd_join_rows(which == 1 ? m.h1s : m.h2s, dst_dev, rows, F, stream);
-    const size_t n4 = (size_t)((rows + 15) / 16) * 16 * F / 4;
-    if (h->half && which != 0)   // h1/h2 are GEMM operands (fp16 in that mode); xe never is
+    if (!enc && m.h_split) return nd_join_rows(which == 1 ? m.h1s : m.h2s, dst_dev, rows, W, stream);
+    const size_t n4 = (size_t)((rows + 15) / 16) * 16 * W / 4;
+    if (h->half && which != 0)   // e0/e1/h1/h2 are GEMM operands (fp16 in that mode); xe never is
         hipLaunchKernelGGL(k_unpack_rows_h, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const _Float16*>(src), dst_dev, rows, F);
+                           reinterpret_cast<const _Float16*>(src), dst_dev, rows, W);
     else
-        hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst_dev, rows, F);
+        hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst_dev, rows, W);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

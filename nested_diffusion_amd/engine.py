@@ -122,8 +122,10 @@ class EnsembleEngine:
         self._x_keepalive = x
 
     def member_buffer(self, k: int, which: int, rows: int) -> torch.Tensor:
-        """Copy of an internal buffer: which = 0 xe [rows,F], 1 h1, 2 h2 (tests only)."""
-        out = torch.empty(rows, self.F, dtype=torch.float32, device=self.device)
+        """Copy of an internal buffer: which = 0 xe [rows,F], 1 h1, 2 h2; 3 e0 [rows,H], 4 e1 (tests only)."""
+        if which not in (0, 1, 2, 3, 4):
+            raise ValueError(f"which={which} unknown")
+        out = torch.empty(rows, self.H if which >= 3 else self.F, dtype=torch.float32, device=self.device)
         check(self.lib.nd_member_buffer(self.h, k, which, ptr(out), rows, self._stream()), "nd_member_buffer")
         return out
 

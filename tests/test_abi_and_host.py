@@ -68,6 +68,23 @@ def test_abi_argument_validation_without_gpu():
     assert lib.nd_set_input_flag(h, None) < 0 and b"workspace" in lib.nd_last_error()          # needs a bound workspace (it resets a device counter)
     assert lib.nd_skinny_row_fragments(32) == 2 and lib.nd_skinny_row_fragments(70) == 5 and lib.nd_skinny_row_fragments(64) == 4
     assert lib.nd_skinny_row_fragments(16) == 1 and lib.nd_skinny_row_fragments(0) < 0
+    # nd_member_buffer checks its arguments before the handle's state (max_batch = max_rows = 32, 5 members here): which = 0 xe,
+    # 1 h1, 2 h2, 3 e0, 4 e1; the encoder's buffers (0, 3, 4) hold at most max_batch rows
+    small = ctypes.c_void_p()
+    assert lib.nd_create(ctypes.byref(_lib.NdConfig(2, 48, 64, 64, 10, 2, 4, 12)), ctypes.byref(small)) == 0
+    for which in (-1, 5, 99):
+        assert lib.nd_member_buffer(small, 0, which, 0x1000, 1, None) == -1 and b"which=" in lib.nd_last_error()       # ND_ERR_ARG
+    for which, name in ((0, b"xe"), (3, b"e0"), (4, b"e1")):
+        assert lib.nd_member_buffer(small, 0, which, 0x1000, 5, None) == -1                                            # rows > max_batch
+        assert name + b" holds at most max_batch rows" in lib.nd_last_error(), lib.nd_last_error()
+    for which in range(5):
+        assert lib.nd_member_buffer(small, 0, which, 0x1000, 13, None) == -1 and b"rows" in lib.nd_last_error()        # rows > max_rows
+        assert lib.nd_member_buffer(small, 0, which, 0x1000, 0, None) == -1
+        assert lib.nd_member_buffer(small, 2, which, 0x1000, 1, None) == -1 and b"member" in lib.nd_last_error()
+        assert lib.nd_member_buffer(small, 0, which, None, 1, None) == -1
+        assert lib.nd_member_buffer(small, 0, which, 0x1000, 4, None) == -3 and b"workspace" in lib.nd_last_error()    # valid: ND_ERR_STATE
+    assert lib.nd_member_buffer(small, 0, 1, 0x1000, 12, None) == -3 and lib.nd_member_buffer(None, 0, 3, 0x1000, 1, None) == -1
+    assert lib.nd_destroy(small) == 0
     assert lib.nd_destroy(h) == 0
     assert lib.nd_linear(None, None, None, None, None, 1, 16, 1, 0, 0, None, 0, None) != 0
     assert lib.nd_packed_bytes(3, 32, 0) == 16 * 32 * 4            # rows padded to 16
@@ -337,6 +354,38 @@ def test_step_plan_restatement_and_branch_search_without_gpu():
                 for half in ((False, True) if F % 32 == 0 else (False,)):
                     assert_plan_matches_library(step_launch(F, M, nm, half, 256))
     assert {L["split"] for L in shapes.values() if L["kernel"] == "k_cond_gemm_b9"} >= {1, 2, 3, 4}
+
+def test_stream_plan_restatement_and_branch_search_without_gpu():
+    """The launch plan of the weight-streaming Linear restated in tests/test_gpu_stream_edges.py (row fragments, workgroups per
+    member under the six-fragment limit, the split-K cost search, cps / S, the nontemporal and dynamic-LDS switches, the route of
+    nd_linear and its workspace) against nd_skinny_plan / nd_skinny_row_fragments / nd_linear_workspace_bytes at the 256 CUs the
+    library assumes without a device, over a sweep and over every shape its branch search picks; the searched shapes reach every
+    branch that file must cover."""
+    from test_gpu_stream_edges import all_linear_shapes, assert_route_matches_library, check_linear_coverage, sweep_plans
+    shapes = all_linear_shapes(256)
+    for R in shapes.values():
+        assert_route_matches_library(R)
+    check_linear_coverage(shapes)
+    sweep_plans(256)
+    # other CU counts (partitioned devices): the restated search still reaches every branch
+    for ncu in (64, 304):
+        check_linear_coverage(all_linear_shapes(ncu))
+
+
+def test_encoder_splitk_slabs_fit_what_the_load_reserves():
+    """nd_encode launches the first encoder layer as a multi-member split-K stream whose S comes from a launch plan at (B, nm), while
+    `carve` reserves data_dim / 16 / 64 + 1 slabs per member at load: S <= that for every B <= max_batch and nm <= K, from the
+    library's own plan (256 CUs without a device) and from the restated plan at other CU counts."""
+    from test_gpu_stream_edges import assert_encoder_slabs_fit
+    for half in (False, True):
+        for D in (16384, 16416, 16384 + 32 * 37, 20000 // 32 * 32, 65536, 150528):
+            for H in (32, 96, 160, 4096):
+                for B in (1, 15, 16, 17, 33, 64, 65, 70, 80, 81, 128):
+                    for nm in (1, 2, 3, 5, 8, 9, 16):
+                        assert_encoder_slabs_fit(D, H, B, nm, half)
+                        for ncu in (32, 64, 304):
+                            assert_encoder_slabs_fit(D, H, B, nm, half, ncu)
+
 
 def test_step_gemm_loops_keep_counted_waits():
     """ISA check (no GPU): every software-pipelined k_skinny loop must wait with a counted vmcnt and contain no flat_load --
