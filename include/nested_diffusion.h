@@ -460,8 +460,9 @@ int nd_linf_random_start(const float *x0_dev, float *out_dev, int B, size_t per_
  *   nd_apgd_control       per-image state of one iteration, one thread per image.  iter = -1 initialises from the start point:
  *                         acc = pred, loss_best = loss_best_last_check = loss, reduced_last_check = 1, step = step0 (2 eps),
  *                         loss_steps [n_iter, B] = 0, flags = 0.  0 <= iter < n_iter: pred = (argmax logits == label; the first maximal
- *                         index, a NaN logit never wins), acc &= pred, loss_steps[iter] = loss, improved = loss > loss_best (then
- *                         loss_best = loss); k > 0 is a checkpoint of length k (the host passes the fixed schedule, 0 <= k <= iter+1):
+ *                         index, a NaN logit never wins in any column; a row whose logits are all NaN yields index 0), acc &= pred,
+ *                         loss_steps[iter] = loss, improved = loss > loss_best (then loss_best = loss); k > 0 is a checkpoint of
+ *                         length k (the host passes the fixed schedule, 0 <= k <= iter+1):
  *                         cnt = #{c < k : loss_steps[iter-c] > loss_steps[iter-c-1]} (row -1 is row n_iter-1, torch's negative index),
  *                         osc = cnt <= k * rho || (!reduced_last_check && loss_best_last_check >= loss_best), reduced_last_check = osc,
  *                         loss_best_last_check = loss_best, and where osc: step /= 2 and restore.  flags [B] int32 =

@@ -35,7 +35,10 @@ autoattack.py (all arrays per image; every operation one rounded fp32 op in this
                 k = max(k - size_decr, n_iter_min);  counter3 = 0
         return acc, x_best_adv
 
-Deviations, documented: sign(NaN) = 0 (a NaN gradient makes no step); argmax ties go to the first maximal index; the random start
+Deviations, documented: sign(NaN) = 0 (a NaN gradient makes no step); argmax ties go to the first maximal index, and inside
+attack_single_run (nd_apgd_control) a NaN logit never wins in any column and a row of NaN logits alone yields index 0, whereas the rows
+run_standard_evaluation and perturb select on the host use torch.argmax, where a NaN logit wins: the two differ only for a model
+that returns NaN logits, whose row the host then counts as predicting the NaN's class; the random start
 draws from the library's Philox keyed on (seed, the image's global index, element, restart) -- the same image starts from the same
 point in any batch, subset or rank -- where the reference draws from torch.rand seeded with time.time(); seed=None becomes 0.
 

@@ -488,10 +488,12 @@ __global__ __launch_bounds__(64) void k_apgd_control(const float* __restrict__ l
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const float* l = logits + (size_t)b * C;
-    int arg = 0;                                        // argmax: the first maximal index (a NaN logit never wins)
+    int arg = 0;                                        // argmax: the first maximal index (a NaN logit never wins; all NaN: index 0)
     float best = l[0];
-    for (int c = 1; c < C; ++c)
-        if (l[c] > best) { best = l[c]; arg = c; }
+    for (int c = 1; c < C; ++c) {
+        const float v = l[c];
+        if (v > best || (best != best && v == v)) { best = v; arg = c; }      // a NaN held from column 0 yields to the first number
+    }
     const bool pred = (int64_t)arg == labels[b];
     const float lb = loss[b];
     if (iter < 0) {

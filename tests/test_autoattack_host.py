@@ -139,3 +139,73 @@ def test_apgd_kernels_refuse_bad_arguments_before_any_launch():
     for call, msg in cases:
         assert call() == -1, msg                                   # ND_ERR_ARG
         assert re.search(msg, lib.nd_last_error()), (msg, lib.nd_last_error())
+
+
+@pytest.mark.parametrize("rho", [0.75, 0.5])
+def test_apgd_restatements_agree_bit_for_bit_on_a_synthetic_run(rho):
+    """The oracle of tests/test_gpu_apgd_edges.py checked where no GPU is needed: ref_control and ref_update (per-kernel, numpy, a literal
+    transcription of the listing) against HostAPGD (whole-array torch, in autopgd_base.py's style, written independently) over one random
+    synthetic run of the production schedule: every state array, every iteration, bit for bit."""
+    import numpy as np
+    from nested_diffusion_amd.autoattack import apgd_schedule
+    from test_gpu_apgd import HostAPGD
+    from test_gpu_apgd_edges import ref_control, ref_new_state, ref_update, same
+    B, C, n_iter, eps, shape = 384, 3, 100, 8 / 255, (3, 2, 2)
+    per = int(np.prod(shape))
+    schedule = apgd_schedule(n_iter, 22, 6, 3)
+    assert len(schedule) == 8
+    rng = np.random.default_rng(77)
+    f32 = np.float32
+
+    level, rise = np.zeros(B, f32), np.linspace(0.0, 1.0, B)
+
+    def draw():
+        logits = rng.standard_normal((B, C)).astype(f32)
+        grad = rng.standard_normal((B, per)).astype(f32)
+        grad[rng.random((B, per)) < 0.05] = 0.0
+        grad[rng.random((B, per)) < 0.02] = np.nan
+        grad[rng.random((B, per)) < 0.02] = np.inf
+        level[:] = level + np.where(rng.random(B) < rise, f32(0.25), f32(-0.25)) * (rng.random(B) < 0.9).astype(f32)
+        loss = level.copy()                                        # a walk per row that rises with the row's own probability, with ties
+        loss[rng.random(B) < 0.01] = np.nan
+        loss[rng.random(B) < 0.01] = np.inf
+        return logits, grad, loss
+
+    x = rng.random((B, per), dtype=f32)
+    x[rng.random((B, per)) < 0.1] = 0.0
+    x[rng.random((B, per)) < 0.1] = 1.0
+    x_adv = np.clip(x + f32(eps) * (f32(2.0) * rng.random((B, per), dtype=f32) - f32(1.0)), f32(0.0), f32(1.0))
+    y = rng.integers(0, C, B)
+    t4 = lambda a: torch.from_numpy(a.copy()).reshape(B, *shape)                                   # noqa: E731
+    logits, grad, loss = draw()
+    host = HostAPGD(t4(x), torch.from_numpy(y), eps, n_iter, schedule, rho=rho)
+    host.init(t4(x_adv), torch.from_numpy(logits), t4(grad), torch.from_numpy(loss))
+    host.do_step(0)
+    st = ref_new_state(B, n_iter)
+    ref_control(st, logits, y, loss, -1, 0, rho, step0=2.0 * eps)
+    a = dict(x=x, x_adv=x_adv, x_adv_old=x_adv.copy(), grad=grad, x_best=x_adv.copy(), grad_best=grad.copy(), x_best_adv=x_adv.copy())
+    ref_update(a, None, st["step"], eps, 1.0, True)
+
+    def compare(where):
+        for n in ("x_adv", "x_adv_old", "x_best", "grad_best", "x_best_adv"):
+            same(n, getattr(host, n).reshape(B, per), a[n], where)
+        for n in ("step", "loss_best", "loss_best_last_check", "loss_steps"):
+            same(n, getattr(host, n), st[n], where)
+        same("reduced_last_check", host.reduced_last_check.to(torch.int32), st["reduced_last_check"], where)
+        same("acc", host.acc.to(torch.int32), st["acc"], where)
+
+    compare("after the first step")
+    seen = set()
+    for i in range(n_iter):
+        logits, grad, loss = draw()
+        host.observe(i, torch.from_numpy(logits), t4(grad), torch.from_numpy(loss))
+        if i + 1 < n_iter:
+            host.do_step(i + 1)
+        a["grad"] = grad
+        ref_control(st, logits, y, loss, i, schedule.get(i, 0), rho)
+        ref_update(a, st["flags"], st["step"], eps, 0.75, i + 1 < n_iter)
+        compare(f"after iteration {i}")
+        seen |= set(int(v) for v in st["flags"])
+    assert seen == set(range(8))                                   # the run passed every flag value from control to update
+    assert host.restores >= B and host.keeps >= B // 2             # and both outcomes of the checkpoint rule, many times
+    assert len(set(st["step"].tolist())) >= 4

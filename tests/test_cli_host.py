@@ -154,7 +154,17 @@ def test_tensor_key_cannot_be_forged_by_a_recycled_address():
             assert not key.matches(b), "a recycled address passed for the freed tensor"
             break
     if not hit:
-        pytest.skip("the host allocator never handed the freed block back")
+        # the host allocator never handed the freed block back (a fragmented heap cycles through several free blocks of this size):
+        # put the new tensor on the freed one's address by hand, over a block that outlives both
+        import numpy as np
+        block = np.zeros(1 << 16, np.float32)
+        a = torch.from_numpy(block)
+        key, ptr = _TensorKey(a), a.data_ptr()
+        assert key.matches(a)
+        del a
+        b = torch.from_numpy(block)
+        assert b.data_ptr() == ptr and b._version == 0 and tuple(b.shape) == (1 << 16,)
+        assert not key.matches(b), "a recycled address passed for the freed tensor"
     c = torch.zeros(8)
     k = _TensorKey(c)
     c.add_(1)
