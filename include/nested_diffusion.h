@@ -488,6 +488,63 @@ int nd_apgd_update(const float *x_dev, float *x_adv_dev, float *x_adv_old_dev, c
                    float *grad_best_dev, float *x_best_adv_dev, const int32_t *flags_dev, const float *step_dev, int B, size_t per_image,
                    float eps, float a, int do_step, void *stream);
 
+/* ---- the L2 attacks (foolbox 3.x L2BasicIterativeAttack / L2ProjectedGradientDescentAttack) and Carlini & Wagner's L2 attack
+ * (L2CarliniWagnerAttack); the listings: nested_diffusion_amd/attack.py.  B images of per_image fp32 elements (per_image % 4 == 0,
+ * 1 <= B <= 65535, images 16-byte aligned); every elementwise operation one rounded fp32 op in the listing's order (contraction off).
+ * No entry point allocates, copies synchronously or synchronises.  Row reductions use no floating-point atomics: nd_l2_parts(per_image)
+ * workgroups per image each write one partial into the workspace, and a finishing pass folds them in a fixed order; the shape
+ * depends on per_image alone, so a norm has the same bits on every run and at every batch size.  ws: 2 * ND_L2_MAX_PARTS * B floats
+ * (nd_l2_random_start: ND_L2_MAX_PARTS * B).  The per-image norms are written out: exactly the values the elementwise pass used.
+ *   nd_margin_head_bwd    Carlini & Wagner's head, beside nd_xent_head_bwd: other [B] int32 = the first maximal index of logits over the
+ *                         non-label columns (a NaN logit never wins; no number among them: the first non-label column),
+ *                         margin [B] = logits[label] - logits[other] + confidence, dlogits = +consts[b] at the label and -consts[b] at
+ *                         other where margin > 0, else 0, dfeat [B, E] = dlogits . head_w ([C, E]): the gradient of
+ *                         sum_b consts[b] * max(0, margin[b]).  At margin == 0 the gradient is 0 (torch's maximum would pass half).
+ *                         2 <= C <= 1024.  A label outside [0, C): margin NaN, other -1, dfeat 0.
+ *   nd_l2_step            gnorm [B] = sqrt(sum g^2); t = x + alpha * (g * (1 / max(gnorm, 1e-12))); d = t - x0;
+ *                         dnorm [B] = sqrt(sum d^2) of the fp32 d actually formed; out = clip(x0 + d * min(1, eps / max(dnorm, 1e-12)),
+ *                         lo, hi).  A NaN anywhere in a row's gradient (gnorm NaN), or a gnorm that overflows, makes that row take no
+ *                         step (t = x), the convention of nd_linf_step.  grad NULL: no step and gnorm (may be NULL) = 0; with
+ *                         lo = -inf, hi = inf that is foolbox's final clip_perturbation.
+ *   nd_l2_random_start    foolbox's uniform_n_balls start: out = clip(x0 + eps * (z / snorm), lo, hi), z the first n = per_image of
+ *                         n + 2 standard normals, snorm [B] = sqrt(sum over all n + 2).  Normal 4q + e of image b comes from
+ *                         Philox4x32-10 with key = (seed low word, seed high word) and counter = (first_image + b, q, restart,
+ *                         ND_L2_START_TAG), the four words mapped by the Box-Muller of nd_rng (words 0, 1 -> normals 0, 1; words 2, 3
+ *                         -> normals 2, 3).  Quads 0 .. per_image / 4 are drawn; the last supplies normals n and n + 1, its other two
+ *                         are discarded.  The counter is keyed on the global image index: a sub-batch draws what it draws in the full
+ *                         batch.
+ *   nd_cw_attack_space    a = (lo + hi) / 2, b = (hi - lo) / 2: w0 = atanhf(((x0 - a) / b) * 0.999999f), xrec = tanhf(w0) * b + a.
+ *                         n elements, n % 4 == 0.
+ *   nd_cw_model_space     t = tanhf(w0 + delta), x = t * b + a, both stored; sq_rec [B] = sum (x - xrec)^2, sq_x0 [B] = sum (x - x0)^2.
+ *   nd_cw_control         one thread per image: adv = argmax(logits + confidence * onehot(label)) != label (the first maximal index, a
+ *                         NaN never wins, all NaN: index 0), found |= adv, norm = sqrt(sq_x0), new_best = adv && norm < best_norm,
+ *                         best_norm = norm where new_best, flags [B] = new_best, loss [B] = consts * max(0, margin) + sq_rec (a NaN
+ *                         margin counts as 0).  found, flags int32 [B].  2 <= C <= 1024.
+ *   nd_cw_update          one pass per element: where flags[b] (flags may be NULL), best = x; then
+ *                         g = ((dx + 2 * (x - xrec)) * b_half) * (1 - t * t); m = 0.9 m + 0.1 g; v = 0.999 v + 0.001 (g * g);
+ *                         delta = delta - (stepsize * (m / bc1)) / (sqrtf(v / bc2) + 1e-8).  bc1 = 1 - 0.9^(k+1), bc2 = 1 - 0.999^(k+1),
+ *                         computed by the host in double.  No transcendental: sqrtf and division only.
+ * One CW iteration on a stream is nd_cw_model_space, the margin gradient, nd_cw_control, nd_cw_update. */
+#define ND_L2_START_TAG 0x4C325331u
+#define ND_L2_MAX_PARTS 256
+int nd_l2_parts(size_t per_image);
+int nd_margin_head_bwd(const float *logits_dev, const int64_t *labels_dev, const float *consts_dev, const float *head_w_dev,
+                       float *dfeat_dev, float *margin_dev, int32_t *other_dev, int B, int C, int E, float confidence, void *stream);
+int nd_l2_step(const float *x_dev, const float *x0_dev, const float *grad_dev, float *out_dev, float *gnorm_dev, float *dnorm_dev,
+               float *ws_dev, int B, size_t per_image, float alpha, float eps, float lo, float hi, void *stream);
+int nd_l2_random_start(const float *x0_dev, float *out_dev, float *snorm_dev, float *ws_dev, int B, size_t per_image, uint64_t seed,
+                       uint32_t first_image, uint32_t restart, float eps, float lo, float hi, void *stream);
+int nd_cw_attack_space(const float *x0_dev, float *w0_dev, float *xrec_dev, size_t n, float lo, float hi, void *stream);
+int nd_cw_model_space(const float *w0_dev, const float *delta_dev, const float *x0_dev, const float *xrec_dev, float *t_dev,
+                      float *x_dev, float *sq_rec_dev, float *sq_x0_dev, float *ws_dev, int B, size_t per_image, float lo, float hi,
+                      void *stream);
+int nd_cw_control(const float *logits_dev, const int64_t *labels_dev, const float *consts_dev, const float *margin_dev,
+                  const float *sq_rec_dev, const float *sq_x0_dev, float *best_norm_dev, int32_t *found_dev, int32_t *flags_dev,
+                  float *loss_dev, int B, int C, float confidence, void *stream);
+int nd_cw_update(float *delta_dev, float *m_dev, float *v_dev, const float *dx_dev, const float *x_dev, const float *xrec_dev,
+                 const float *t_dev, float *best_dev, const int32_t *flags_dev, int B, size_t per_image, float stepsize, float bc1,
+                 float bc2, float b_half, void *stream);
+
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */
 /* add_noise (:272-279): out = x + z * std, z = the randn_like draw (supplied, like the sampler's noise). */

@@ -168,6 +168,14 @@ SIGNATURES = {
     "nd_apgd_random_start": (_i, [_vp, _vp, _vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
     "nd_apgd_control": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "nd_apgd_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _i, _vp]),
+    "nd_l2_parts": (_i, [_sz]),
+    "nd_margin_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "nd_l2_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _vp]),
+    "nd_l2_random_start": (_i, [_vp, _vp, _vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_cw_attack_space": (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp]),
+    "nd_cw_model_space": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _vp]),
+    "nd_cw_control": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "nd_cw_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _vp]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
 }
 

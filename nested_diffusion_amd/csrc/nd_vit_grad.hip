@@ -10,6 +10,7 @@
 //   k_gelu_bwd_split    du = dg * gelu'(u) (exact erf), written as the fc1-dX operand image
 //   k_attention_bwd     dq, dk, dv of softmax(q k^T / 8) v for one (image, head) per workgroup: P recomputed from q and k
 //   k_xent_head_bwd     softmax(logits) - onehot(label) times head.weight; per-image cross-entropy
+//   k_margin_head_bwd   Carlini & Wagner's head: the gradient of c * max(0, logit margin) times head.weight; margin and runner-up
 //   k_unpatchify        inverse permutation of k_patchify (stride == kernel: no overlap)
 //   k_linf_step         x0 + clip(x + a sign(g) - x0, -eps, eps), clipped to the bounds (foolbox's order)
 //   k_linf_start        x0 + U[-eps, eps) from Philox4x32-10, clipped to the bounds
@@ -364,6 +365,59 @@ __global__ __launch_bounds__(256) void k_xent_head_bwd(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// Carlini & Wagner's head: the gradient of c * max(0, margin), margin = logits[label] - logits[other] + confidence, other = the first
+// maximal index over the non-label columns (a NaN logit never wins; no number among them: the first non-label column).  dlogits is +c at
+// the label and -c at other where margin > 0, else 0 (at margin == 0 the gradient is 0, where torch's maximum passes half);
+// dfeat = dlogits . head_w, the two terms joined in column order as a sum over all columns would.  One workgroup per image; a label
+// outside [0, C) gives margin NaN, other -1 and a zero gradient.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_margin_head_bwd(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                         const float* __restrict__ consts, const float* __restrict__ w, float* __restrict__ dfeat,
+                                                         float* __restrict__ margin, int32_t* __restrict__ other, int C, int E, float confidence) {
+    __shared__ int s_other;
+    __shared__ float s_margin;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float* l = logits + (size_t)b * C;
+    const int64_t y = labels[b];
+    const bool valid = y >= 0 && y < C;
+    if (t < 64) {
+        int arg = 0x7FFFFFFF;                            // no number seen yet
+        float best = 0.f;
+        for (int c = t; c < C; c += 64) {
+            const float v = l[c];
+            if (c != y && v == v && (arg == 0x7FFFFFFF || v > best)) { best = v; arg = c; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(best, off, 64);
+            const int oa = __shfl_xor(arg, off, 64);
+            if (oa != 0x7FFFFFFF && (arg == 0x7FFFFFFF || ov > best || (ov == best && oa < arg))) { best = ov; arg = oa; }
+        }
+        if (t == 0) {
+            if (arg == 0x7FFFFFFF) arg = y == 0 ? 1 : 0;
+            s_other = valid ? arg : -1;
+            s_margin = valid ? (l[y] - l[arg]) + confidence : NAN;
+            other[b] = s_other;
+            margin[b] = s_margin;
+        }
+    }
+    __syncthreads();
+    const float c = consts[b];
+    const bool on = s_margin > 0.f;
+    const int o = s_other, yi = (int)y;
+    const int c1 = yi < o ? yi : o, c2 = yi < o ? o : yi;
+    const float d1 = yi < o ? c : -c, d2 = yi < o ? -c : c;
+    for (int e = t; e < E; e += 256) {
+        float a = 0.f;
+        if (on) {
+            a = __builtin_fmaf(d1, w[(size_t)c1 * E + e], a);
+            a = __builtin_fmaf(d2, w[(size_t)c2 * E + e], a);
+        }
+        dfeat[(size_t)b * E + e] = a;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // un-patchify: img[b][c][py*p+iy][px*p+ix] = cols[(b, py, px)][c*p*p + iy*p + ix]; 4 consecutive pixels of a row per thread
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_unpatchify(const float* __restrict__ cols, float* __restrict__ img, int B, int Cin, int Himg, int Wimg, int p) {
@@ -638,6 +692,16 @@ extern "C" int nd_xent_head_bwd(const float* logits, const int64_t* labels, cons
     if (!logits || !labels || !head_w || !dfeat) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (B < 1 || C < 1 || C > 1024 || E < 1) return nd_set_err(ND_ERR_ARG, "xent_head_bwd needs 1 <= C <= 1024 (C=%d)", C);
     hipLaunchKernelGGL(k_xent_head_bwd, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, labels, head_w, dfeat, loss, C, E);
+    HIP_CHECK(hipGetLastError());
+    return ND_OK;
+}
+
+extern "C" int nd_margin_head_bwd(const float* logits, const int64_t* labels, const float* consts, const float* head_w, float* dfeat,
+                                  float* margin, int32_t* other, int B, int C, int E, float confidence, void* stream) {
+    if (!logits || !labels || !consts || !head_w || !dfeat || !margin || !other) return nd_set_err(ND_ERR_ARG, "NULL tensor");
+    if (B < 1 || C < 2 || C > 1024 || E < 1) return nd_set_err(ND_ERR_ARG, "margin_head_bwd needs 2 <= C <= 1024 (C=%d)", C);
+    hipLaunchKernelGGL(k_margin_head_bwd, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, logits, labels, consts, head_w, dfeat, margin, other,
+                       C, E, confidence);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

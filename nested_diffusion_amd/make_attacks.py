@@ -1,6 +1,6 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
-    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|AUTOPGD --eps E --out ROOT \
+    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD --eps E --out ROOT \
         [--preprocess grayscaled] [--seed S] [--batch_size B]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
@@ -8,6 +8,7 @@ test split (the PGD / APGD random start of an image is keyed on its index in the
 as RGB uint8 = round(255 * adv), with the classes and file stems of the source: the tree data_loader_attacks reads
 (dataset_helper/chest_x_ray_dataset.py:197-227; here data.get_dataset with a *Atk<NAME> dataset name).  AUTOPGD is the reference's
 AutoAttack(vit, eps=eps, version='custom', norm='Linf', attacks_to_run=['apgd-ce']) run by run_standard_evaluation on each batch.
+A Carlini & Wagner set is written from Python: write_attacked_set(config, attack.CarliniWagner(eps, vit, ...), "CW", out).
 """
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ import torch
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="write an attacked test set (Test_attacks_<NAME>) with the GPU attacks of attack.py")
     p.add_argument("--config", type=str, required=True)
-    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "AUTOPGD"], required=True)
+    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "BIM", "L2PGD", "AUTOPGD"], required=True)
     p.add_argument("--eps", type=float, required=True)
     p.add_argument("--out", type=str, required=True, help="root the Test_attacks_<NAME> tree is written under")
     p.add_argument("--preprocess", type=str, choices=["grayscaled", "standardized"], default="grayscaled")
@@ -33,41 +34,42 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def main(argv=None) -> int:
-    from PIL import Image
-
-    from . import main as nd_main
-    from .attack import Attack
-    from .autoattack import AutoAttack
-    from .data import get_dataset
+def load_vit(config, device):
+    """The ViT checkpoint the runner would load for the config's dataset."""
     from .mapping import VisionTransformer, load_pickled
     from .runner import CHEST
 
-    args = build_parser().parse_args(argv)
-    with open(args.config) as f:
-        import yaml
-        config = nd_main.dict2namespace(yaml.safe_load(f))
-    if args.dataroot is not None:
-        config.data.dataroot = args.dataroot
     base = config.data.dataset.split("Atk", 1)[0].replace("Validate", "")
-    config.data.dataset = base                          # the clean test split of the config's dataset
-    ds = get_dataset(args, config)
-    device = torch.device("cuda", args.device)
     ckpt = "ChestXRay" if base in CHEST else "ISICSkinCancer"
     sd = load_pickled(os.path.join(config.diffusion.trained_aux_cls_ckpt_path, f"vit_base_patch16_224_{ckpt}.pth"))
-    vit = VisionTransformer(sd, max(1, sd["patch_embed.proj.weight"].shape[0] // 64), device)
-    if args.attack_name == "AUTOPGD":
-        attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
-    else:
-        attack = Attack(args.eps, args.attack_name, vit, seed=args.seed)
-    out_root = os.path.join(args.out, f"Test_attacks_{args.attack_name}")
+    return VisionTransformer(sd, max(1, sd["patch_embed.proj.weight"].shape[0] // 64), device)
+
+
+def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
+                       device=None) -> int:
+    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner or an AutoAttack, which
+    holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
+    import types
+
+    from PIL import Image
+
+    from .autoattack import AutoAttack
+    from .data import get_dataset
+
+    if dataroot is not None:
+        config.data.dataroot = dataroot
+    config.data.dataset = config.data.dataset.split("Atk", 1)[0].replace("Validate", "")     # the clean test split of the config's dataset
+    ds = get_dataset(types.SimpleNamespace(preprocess=preprocess), config)
+    vit = attack.model
+    device = vit.device if device is None else device
+    out_root = os.path.join(out, f"Test_attacks_{name}")
     n_ok = 0
-    for start in range(0, len(ds), args.batch_size):
-        idx = list(range(start, min(start + args.batch_size, len(ds))))
+    for start in range(0, len(ds), batch_size):
+        idx = list(range(start, min(start + batch_size, len(ds))))
         items = [ds[i] for i in idx]
         x = torch.stack([it[0] for it in items]).to(device)
         y = torch.tensor([it[1] for it in items], dtype=torch.int64, device=device)
-        if args.attack_name == "AUTOPGD":
+        if isinstance(attack, AutoAttack):
             adv = attack.run_standard_evaluation(x, y, bs=len(idx), first_image=start)
             success = vit.forward(adv).argmax(dim=1) != y
         else:
@@ -80,7 +82,26 @@ def main(argv=None) -> int:
             os.makedirs(d, exist_ok=True)
             stem = os.path.splitext(os.path.basename(path))[0]
             Image.fromarray(np.ascontiguousarray(pix[k]), "RGB").save(os.path.join(d, stem + ".png"))
-    print(f"{args.attack_name} eps={args.eps}: {len(ds)} images written under {out_root}, {n_ok} successful attacks")
+    print(f"{name} eps={attack.epsilon}: {len(ds)} images written under {out_root}, {n_ok} successful attacks")
+    return n_ok
+
+
+def main(argv=None) -> int:
+    from . import main as nd_main
+    from .attack import make_attack
+    from .autoattack import AutoAttack
+
+    args = build_parser().parse_args(argv)
+    with open(args.config) as f:
+        import yaml
+        config = nd_main.dict2namespace(yaml.safe_load(f))
+    device = torch.device("cuda", args.device)
+    vit = load_vit(config, device)
+    if args.attack_name == "AUTOPGD":
+        attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
+    else:
+        attack = make_attack(args.eps, args.attack_name, vit, seed=args.seed)
+    write_attacked_set(config, attack, args.attack_name, args.out, args.preprocess, args.batch_size, args.dataroot, device)
     return 0
 
 

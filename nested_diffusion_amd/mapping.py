@@ -169,17 +169,16 @@ class VisionTransformer:
         dh = ops.gemm_split(dqkv, wT[pre + "attn.qkv.weight"])
         return ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh, LN_EPS, residual=dx2, want_split=True)
 
-    def input_grad(self, x: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(logits, dx, loss): the forward (the same kernels in the same order as forward(): its logits equal forward(x) bit for bit),
-        then the gradient of crossentropy(logits, labels).sum() -- foolbox's loss -- with respect to the input image x [B, 3, H, W],
-        and the per-image cross-entropy."""
+    def _forward_recorded(self, x: torch.Tensor):
+        """The forward of forward(), same kernels in the same order, keeping what the input gradient needs:
+        (logits, cls_in, recs, B, N, H, W)."""
         x = ops._f32(x, "x")
         B, _, H, W = x.shape
         n_tok = (H // self.patch) * (W // self.patch) + 1
         if n_tok > ops.ATTENTION_BWD_MAX_TOKENS:         # refused before the forward runs, not by the first attention backward after it
             raise _lib.NdError(f"input_grad: the attention backward takes N <= {ops.ATTENTION_BWD_MAX_TOKENS} tokens per image "
                                f"(N={n_tok} for {H} x {W} images, patch {self.patch})")
-        wT = self.transposed_weights()
+        self.transposed_weights()
         tok = self._tokens(x)
         N = tok.shape[0] // B
         recs = []
@@ -189,9 +188,13 @@ class VisionTransformer:
         cls_in = tok.reshape(B, N, self.embed_dim)[:, 0].contiguous()
         cls = ops.layernorm(cls_in, self.p["norm.weight"], self.p["norm.bias"], LN_EPS)
         logits = ops.linear(cls, self.p["head.weight"], self.p["head.bias"])
-        dcls, loss = ops.xent_head_grad(logits, labels, self.p["head.weight"])
+        return logits, cls_in, recs, B, N, H, W
+
+    def _input_backward(self, dcls: torch.Tensor, cls_in: torch.Tensor, recs: list, B: int, N: int, H: int, W: int) -> torch.Tensor:
+        """dL/dx from dcls = dL/d(the final norm's output on the cls token): the backward chain every head gradient shares."""
+        wT = self._wT
         dcls = ops.layernorm_grad(cls_in, self.p["norm.weight"], dcls, LN_EPS)
-        dy = torch.zeros(B, N, self.embed_dim, dtype=torch.float32, device=x.device)
+        dy = torch.zeros(B, N, self.embed_dim, dtype=torch.float32, device=dcls.device)
         dy[:, 0] = dcls                                       # only the cls token reaches the head
         dy = dy.reshape(B * N, self.embed_dim)
         dy_img = ops.split_rows(dy)
@@ -200,7 +203,25 @@ class VisionTransformer:
             recs[i] = None
         dpatch = dy.reshape(B, N, self.embed_dim)[:, 1:].reshape(-1, self.embed_dim).contiguous()   # cls token / pos_embed: no input path
         dcols = ops.gemm_split(dpatch, wT["patch_embed"])
-        return logits, ops.unpatchify(dcols, B, self.in_chans, H, W, self.patch), loss
+        return ops.unpatchify(dcols, B, self.in_chans, H, W, self.patch)
+
+    def input_grad(self, x: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(logits, dx, loss): the forward (the same kernels in the same order as forward(): its logits equal forward(x) bit for bit),
+        then the gradient of crossentropy(logits, labels).sum() -- foolbox's loss -- with respect to the input image x [B, 3, H, W],
+        and the per-image cross-entropy."""
+        logits, cls_in, recs, B, N, H, W = self._forward_recorded(x)
+        dcls, loss = ops.xent_head_grad(logits, labels, self.p["head.weight"])
+        return logits, self._input_backward(dcls, cls_in, recs, B, N, H, W), loss
+
+    def input_grad_margin(self, x: torch.Tensor, labels: torch.Tensor, consts: torch.Tensor, confidence: float = 0.0,
+                          check_labels: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(logits, dx, margin): input_grad's forward and backward chain with Carlini & Wagner's loss at the head: dx is the gradient of
+        sum_b consts[b] * max(0, margin[b]) with respect to x, margin = logits[label] - max over the other logits + confidence
+        (nd_margin_head_bwd; a row whose margin is <= 0 has dx = 0).  check_labels=False skips the label-range check, the call's only
+        read-back."""
+        logits, cls_in, recs, B, N, H, W = self._forward_recorded(x)
+        dcls, margin, _ = ops.margin_head_grad(logits, labels, consts, self.p["head.weight"], confidence, check_labels=check_labels)
+        return logits, self._input_backward(dcls, cls_in, recs, B, N, H, W), margin
 
 
 class GuidingConditioner:
