@@ -523,7 +523,9 @@ int nd_apgd_update(const float *x_dev, float *x_adv_dev, float *x_adv_old_dev, c
  *   nd_cw_update          one pass per element: where flags[b] (flags may be NULL), best = x; then
  *                         g = ((dx + 2 * (x - xrec)) * b_half) * (1 - t * t); m = 0.9 m + 0.1 g; v = 0.999 v + 0.001 (g * g);
  *                         delta = delta - (stepsize * (m / bc1)) / (sqrtf(v / bc2) + 1e-8).  bc1 = 1 - 0.9^(k+1), bc2 = 1 - 0.999^(k+1),
- *                         computed by the host in double.  No transcendental: sqrtf and division only.
+ *                         computed by the host in double.  b_half must be the b of nd_cw_model_space, (hi - lo) / 2 formed in fp32
+ *                         from the fp32 lo and hi, so that the gradient uses the b that produced x.  No transcendental: sqrtf and
+ *                         division only.
  * One CW iteration on a stream is nd_cw_model_space, the margin gradient, nd_cw_control, nd_cw_update. */
 #define ND_L2_START_TAG 0x4C325331u
 #define ND_L2_MAX_PARTS 256

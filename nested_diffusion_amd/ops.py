@@ -2,6 +2,7 @@
 Every function launches HIP kernels on torch's current stream; inputs must live on the GPU."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -706,13 +707,22 @@ def cw_control(logits: torch.Tensor, labels: torch.Tensor, consts: torch.Tensor,
     return s.loss
 
 
+def cw_b_half(lo: float, hi: float) -> float:
+    """b = (hi - lo) / 2 as nd_cw_attack_space and nd_cw_model_space form it: float32 lo and hi, float32 arithmetic (each double operation
+    on float32 operands, rounded to float32, is the float32 operation).  nd_cw_update's b_half must be this value, not the double's rounding:
+    at (-0.3, 1.1) the two differ by an ulp."""
+    r = lambda v: ctypes.c_float(v).value                                  # noqa: E731
+    return r(r(r(hi) - r(lo)) / 2.0)
+
+
 def cw_update(s: CwState, dx: torch.Tensor, xrec: torch.Tensor, stepsize: float, k: int, lo: float = 0.0, hi: float = 1.0,
               use_flags: bool = True) -> None:
     """Iteration k's per-element pass (nd_cw_update), in place on s: best = x in the flagged rows, then the tanh-space gradient of
-    sum_b loss_b from dx and the Adam update of delta with the bias corrections of step k + 1 (computed here in double)."""
+    sum_b loss_b from dx and the Adam update of delta with the bias corrections of step k + 1 (computed here in double).  dx is
+    taken as it is: a non-contiguous one is refused, not copied."""
     shape = tuple(s.delta.shape)
-    dx, xrec = _inplace(_f32(dx, "dx"), "dx", shape=shape), _inplace(xrec, "xrec", shape=shape)
+    dx, xrec = _inplace(dx, "dx", shape=shape), _inplace(xrec, "xrec", shape=shape)
     bc1, bc2 = 1.0 - 0.9 ** (k + 1), 1.0 - 0.999 ** (k + 1)
     check(_lib.load().nd_cw_update(ptr(s.delta), ptr(s.m), ptr(s.v), ptr(dx), ptr(s.x), ptr(xrec), ptr(s.t), ptr(s.best),
-                                   ptr(s.flags) if use_flags else None, s.B, s.per, float(stepsize), bc1, bc2, (float(hi) - float(lo)) / 2.0,
+                                   ptr(s.flags) if use_flags else None, s.B, s.per, float(stepsize), bc1, bc2, cw_b_half(lo, hi),
                                    _stream(dx)), "nd_cw_update")

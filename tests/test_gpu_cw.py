@@ -235,9 +235,9 @@ def test_attack_space_and_model_space():
 
 
 # ---- 3. nd_cw_update -----------------------------------------------------------------------------------------------------------------------
-def adam32(delta, m, v, dx, x, xrec, t, stepsize, k):
+def adam32(delta, m, v, dx, x, xrec, t, stepsize, k, b_half=0.5):
     bc1, bc2 = F32(1.0 - 0.9 ** (k + 1)), F32(1.0 - 0.999 ** (k + 1))
-    g = ((dx + F32(2.0) * (x - xrec)) * F32(0.5)) * (F32(1.0) - t * t)
+    g = ((dx + F32(2.0) * (x - xrec)) * F32(b_half)) * (F32(1.0) - t * t)
     m = F32(0.9) * m + F32(0.1) * g
     v = F32(0.999) * v + F32(0.001) * (g * g)
     return delta - (F32(stepsize) * (m / bc1)) / (np.sqrt(v / bc2) + F32(1e-8)), m, v

@@ -94,11 +94,75 @@ def test_new_entry_points_refuse_bad_arguments_before_any_launch():
         (lambda: lib.nd_cw_control(P, P, P, P, P, P, P, P, P, P, 0, 2, 0.0, None), rb"1 <= B <= 65535"),
         (lambda: lib.nd_cw_control(P, P, P, P, P, P, P, P, P, P, 65536, 2, 0.0, None), rb"1 <= B <= 65535"),
     ]
+    # one misaligned image pointer per call, everything else valid: each position of each entry point that reads or writes float4
+    al = rb"16-byte aligned"
+    for i in range(2):
+        a = [P] * 4
+        a[i] += 4
+        cases.append((lambda a=a: lib.nd_l2_random_start(*a, 2, 8, 1, 0, 0, 1.0, 0.0, 1.0, None), rb"l2 random start needs " + al))
+    for i in range(3):
+        a = [P] * 3
+        a[i] += 4
+        cases.append((lambda a=a: lib.nd_cw_attack_space(*a, 8, 0.0, 1.0, None), rb"cw attack space needs " + al))
+    for i in range(6):
+        a = [P] * 9
+        a[i] += 4
+        cases.append((lambda a=a: lib.nd_cw_model_space(*a, 2, 8, 0.0, 1.0, None), rb"cw model space needs " + al))
+    for i in range(8):
+        a = [P] * 9
+        a[i] += 4
+        cases.append((lambda a=a: lib.nd_cw_update(*a, 2, 8, 0.01, 0.1, 0.001, 0.5, None), rb"cw update needs " + al))
+    assert len(cases) == 16 + 11 + 19
     for call, msg in cases:
         assert call() == -1, msg                                   # ND_ERR_ARG
         assert re.search(msg, lib.nd_last_error()), (msg, lib.nd_last_error())
     # the shape of a row reduction depends on per_image alone
     assert [lib.nd_l2_parts(n) for n in (4, 1024, 1028, 3072, 150528, 4 * 256 * 256, 4 * 256 * 300)] == [1, 1, 2, 3, 147, 256, 256]
+
+
+class _FakeTensor:
+    """What ops' checks ask of a GPU tensor, with no GPU: cw_update hands the fake library nothing but its address."""
+    is_cuda, dtype, device = True, torch.float32, "cuda:0"
+
+    def __init__(self, shape):
+        self.shape = shape
+
+    def is_contiguous(self):
+        return True
+
+    def contiguous(self):
+        return self
+
+    def data_ptr(self):
+        return 4096
+
+
+@pytest.mark.parametrize("lo,hi", [(0.0, 1.0), (-1.0, 1.0), (0.25, 0.75), (-0.3, 1.1), (0.1, 0.9)])
+def test_cw_update_hands_over_the_b_of_the_model_space_pass(lo, hi, monkeypatch):
+    """nd_cw_model_space forms b = (hi - lo) / 2 in float32 from the float32 bounds, and x = t * b + a with it; the tanh-space gradient
+    of nd_cw_update must use the same b.  At (-0.3, 1.1) that is 0.70000005 where the double's rounding is 0.7; at (0.1, 0.9) it is
+    0.39999998 against 0.4."""
+    import ctypes
+    import numpy as np
+    from nested_diffusion_amd import _lib, ops
+    seen = []
+
+    def nd_cw_update(*args):
+        seen.append(args)
+        return 0
+
+    monkeypatch.setattr(_lib, "load", lambda: types.SimpleNamespace(nd_cw_update=nd_cw_update))
+    monkeypatch.setattr(ops, "_stream", lambda t: None)
+    shape = (2, 8)
+    s = types.SimpleNamespace(B=2, per=8, **{n: _FakeTensor(shape) for n in ("delta", "m", "v", "x", "t", "best")}, flags=_FakeTensor((2,)))
+    ops.cw_update(s, _FakeTensor(shape), _FakeTensor(shape), 0.01, 3, lo, hi)
+    (args,) = seen
+    assert len(args) == len(_lib.SIGNATURES["nd_cw_update"][1]) and args[9:11] == (2, 8)
+    want = (np.float32(hi) - np.float32(lo)) / np.float32(2.0)      # the kernel launch's expression: (hi - lo) / 2.0f on float arguments
+    assert ctypes.c_float(args[14]).value == float(want), (args[14], want)
+    assert args[14] == float(want)                                  # and exactly a float32 already: the ABI's conversion rounds nothing
+    if (lo, hi) == (-0.3, 1.1):
+        assert float(want) != float(np.float32((hi - lo) / 2.0))    # the case the double's rounding gets wrong
 
 
 def test_make_attacks_parser_accepts_the_l2_family():
