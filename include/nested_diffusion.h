@@ -488,6 +488,51 @@ int nd_apgd_update(const float *x_dev, float *x_adv_dev, float *x_adv_old_dev, c
                    float *grad_best_dev, float *x_best_adv_dev, const int32_t *flags_dev, const float *step_dev, int B, size_t per_image,
                    float eps, float a, int do_step, void *stream);
 
+/* ---- the Square attack, Linf (autoattack's square.py, the score-based member of AutoAttack; the listing: nested_diffusion_amd/square.py).
+ * B images [B, Cin, H, W] fp32, contiguous (1 <= B <= 65535, 1 <= Cin <= 32, 1 <= H, W <= 4096); a query changes one s x s window per image
+ * (1 <= s <= min(H, W)).  Windows start anywhere and W need not be a multiple of 4: window accesses are scalar fp32, coalesced along w,
+ * and nothing assumes 16-byte alignment inside an image.  Every value is one rounded fp32 op in the listed order (contraction off), so a
+ * float32 restatement on the host reproduces every array bit for bit.  No entry point allocates, copies synchronously or synchronises:
+ * a query (propose, the model's forward pass, accept, commit) can be captured.  Draws are Philox4x32-10 with key = (seed low word, seed
+ * high word), keyed on index: int64 [B], the GLOBAL image index of each row (its low word), so a row of a compacted subset, of another
+ * batch size or of another rank draws what it draws in the full run.  A row is ACTIVE while margin_min[b] > 0; any other value (<= 0,
+ * -0.0, NaN) freezes it.
+ *   nd_square_init        the vertical-stripe start over whole images: x_best[b,c,h,w] = x_new[b,c,h,w] = clip(x0 + eps * sigma(b,c,w), lo, hi).
+ *                         With j = c * W + w, sigma = +1 if the top bit of word j % 4 of philox(counter = (index[b], j / 4, restart,
+ *                         ND_SQUARE_INIT_TAG)) is set, else -1: it does not depend on h.
+ *   nd_square_propose     per active row (a frozen row is not touched at all): p = philox(counter = (index[b], iter, restart,
+ *                         ND_SQUARE_STEP_TAG)); vh = (uint64(p0) * (H - s + 1)) >> 32, vw = (uint64(p1) * (W - s + 1)) >> 32;
+ *                         d_c = +2eps if bit c of p2 is set, else -2eps, 2eps = eps + eps in fp32; over the window [vh, vh + s) x [vw, vw + s)
+ *                         of every channel only: x_new = clip(min(max(x_best + d_c, x0 - eps), x0 + eps), lo, hi); win[b] = (vh, vw),
+ *                         int32 [B, 2].  iter >= 0.
+ *   nd_square_accept      one thread per image.  margin = scores[label] - max_{j != label} scores[j], one fp32 subtraction (the first
+ *                         maximal index wins ties); any NaN score in the row (or a label outside [0, C)) makes the margin NaN, and a NaN
+ *                         margin is never accepted and never counts as fooled.  loss = margin.  iter = -1 initialises: margin_min = margin,
+ *                         loss_min = loss, n_queries = 1, flags = 0.  iter >= 0, only where margin_min > 0 on entry: improved =
+ *                         loss < loss_min (then loss_min = loss); accept = improved || margin <= 0 (then margin_min = margin);
+ *                         n_queries += 1; flags[b] = ND_SQUARE_ACTIVE | (accept ? ND_SQUARE_ACCEPT : 0).  A frozen row gets flags = 0 and
+ *                         nothing else changes.  scores [B, C] fp32 (2 <= C <= 1024), labels int64 [B]; margin_min, loss_min fp32 [B];
+ *                         n_queries, flags int32 [B].
+ *   nd_square_commit      over the window win[b] only (the s of the propose): ACTIVE and ACCEPT: x_best = x_new; ACTIVE alone: x_new = x_best,
+ *                         which takes the candidate back; otherwise nothing.  A corner that does not keep the window inside the image is
+ *                         ignored.  After every commit x_new == x_best on every element of every row: the model reads x_new directly and
+ *                         no per-query copy of an image exists.
+ * The three launches of a query are kept apart on purpose: the window a commit restores and the window the next propose writes overlap
+ * in the same row, and stream order between the two launches keeps "restore, then perturb" in that order. */
+#define ND_SQUARE_INIT_TAG 0x53514931u
+#define ND_SQUARE_STEP_TAG 0x53515331u
+#define ND_SQUARE_ACTIVE 1
+#define ND_SQUARE_ACCEPT 2
+int nd_square_init(const float *x0_dev, const int64_t *index_dev, float *x_best_dev, float *x_new_dev, int B, int Cin, int H, int W,
+                   uint64_t seed, uint32_t restart, float eps, float lo, float hi, void *stream);
+int nd_square_propose(const float *x0_dev, const float *x_best_dev, float *x_new_dev, const int64_t *index_dev, const float *margin_min_dev,
+                      int32_t *win_dev, int B, int Cin, int H, int W, int s, int iter, uint64_t seed, uint32_t restart, float eps, float lo,
+                      float hi, void *stream);
+int nd_square_accept(const float *scores_dev, const int64_t *labels_dev, float *margin_min_dev, float *loss_min_dev, int32_t *n_queries_dev,
+                     int32_t *flags_dev, int B, int C, int iter, void *stream);
+int nd_square_commit(float *x_best_dev, float *x_new_dev, const int32_t *win_dev, const int32_t *flags_dev, int B, int Cin, int H, int W, int s,
+                     void *stream);
+
 /* ---- the L2 attacks (foolbox 3.x L2BasicIterativeAttack / L2ProjectedGradientDescentAttack) and Carlini & Wagner's L2 attack
  * (L2CarliniWagnerAttack); the listings: nested_diffusion_amd/attack.py.  B images of per_image fp32 elements (per_image % 4 == 0,
  * 1 <= B <= 65535, images 16-byte aligned); every elementwise operation one rounded fp32 op in the listing's order (contraction off).

@@ -154,7 +154,8 @@ class AutoAttack:
                                       f"attacks_to_run=['apgd-ce']")
         bad = [a for a in attacks_to_run if a not in IMPLEMENTED]
         if bad:
-            raise NotImplementedError(f"AutoAttack attacks {', '.join(repr(a) for a in bad)} are not implemented (only 'apgd-ce')")
+            raise NotImplementedError(f"AutoAttack attacks {', '.join(repr(a) for a in bad)} are not implemented (only 'apgd-ce'; "
+                                      "Square stands on its own as square.SquareAttack)")
         self.model = _vit(model)
         self.norm, self.epsilon, self.seed, self.verbose = norm, float(eps), seed, verbose
         self.attacks_to_run: List[str] = list(attacks_to_run)

@@ -8,7 +8,8 @@ test split (the PGD / APGD random start of an image is keyed on its index in the
 as RGB uint8 = round(255 * adv), with the classes and file stems of the source: the tree data_loader_attacks reads
 (dataset_helper/chest_x_ray_dataset.py:197-227; here data.get_dataset with a *Atk<NAME> dataset name).  AUTOPGD is the reference's
 AutoAttack(vit, eps=eps, version='custom', norm='Linf', attacks_to_run=['apgd-ce']) run by run_standard_evaluation on each batch.
-A Carlini & Wagner set is written from Python: write_attacked_set(config, attack.CarliniWagner(eps, vit, ...), "CW", out).
+A Carlini & Wagner set is written from Python: write_attacked_set(config, attack.CarliniWagner(eps, vit, ...), "CW", out); so is a
+Square set: write_attacked_set(config, square.SquareAttack(vit, eps=eps), "SQUARE", out) (no dataset name reads that tree back).
 """
 from __future__ import annotations
 
@@ -47,7 +48,7 @@ def load_vit(config, device):
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
                        device=None) -> int:
-    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner or an AutoAttack, which
+    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner, a SquareAttack or an AutoAttack, which
     holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
     import types
 

@@ -376,7 +376,7 @@ class Diffusion(object):
     # ---- test loop ----------------------------------------------------------------------------
     def test_atk(self, test_loader=None, attack=None):
         """:631-840: input perturbations (:726-737), the hot path, and the report the reference prints (accuracy, ECE,
-        per-class PIW and variances, :801-838).  attack: an attack.Attack, L2Attack or CarliniWagner (attack.make_attack) or an autoattack.AutoAttack (AUTOPGD) applied to this rank's
+        per-class PIW and variances, :801-838).  attack: an attack.Attack, L2Attack or CarliniWagner (attack.make_attack), a square.SquareAttack or an autoattack.AutoAttack (AUTOPGD) applied to this rank's
         rows after the perturbations (:738-739; the random start of image i is keyed on its global index).  The --attack_name switch itself still raises."""
         args, config = self.args, self.config
         if getattr(args, "attack_name", None) not in (None, "None"):
