@@ -592,6 +592,34 @@ int nd_cw_update(float *delta_dev, float *m_dev, float *v_dev, const float *dx_d
                  const float *t_dev, float *best_dev, const int32_t *flags_dev, int B, size_t per_image, float stepsize, float bc1,
                  float bc2, float b_half, void *stream);
 
+/* ---- the gradient through the mapping MLPs (csrc/nd_mlp_grad.hip; the chain: mapping.py GuidingConditioner.input_grad).  The ensemble
+ * is conditioned on the mapping networks (patch_embed -> blocks[0..k] -> mlps[k] -> softmax), not on the full ViT's head: these two entry
+ * points, with the ViT block gradients above, give the gradient of the conditioners' own loss with respect to the image.  Neither
+ * allocates, copies synchronously or synchronises; both are capturable.
+ *   nd_linear_bwd         out[M, K] = ((dy[M, N] . W[N, K]) (.) (gate[M, K] > 0)) + add[M, K]: the input gradient of a Linear whose
+ *                         [N, K] weight is held as its nd_pack_rows image ONLY (w_packed_dev, ND_DTYPE_F32; read in place, no transposed
+ *                         or unpacked copy exists anywhere).  dy, gate, add, out: row-major fp32.  gate may be NULL (no mask); otherwise
+ *                         it is the forward's post-ReLU activation and `> 0` is strict: ReLU'(0) = 0 as in torch (+0.0 and -0.0 alike),
+ *                         and a NaN gate gives 0.  add may be NULL and may alias out.  1 <= M <= ND_LINEAR_BWD_MAX_M, K % 16 == 0,
+ *                         N >= 1; the image's zero rows N .. 16 * ceil(N / 16) meet a dy operand that is zero-filled in registers and
+ *                         never read from memory.  An ND_DTYPE_F16 image is refused (ND_ERR_ARG).  No workspace.
+ *                         A workgroup owns a range of W's 16-column blocks and walks all row blocks for them: no split over the
+ *                         contraction, no atomics, no second pass.  Exact-f32 MFMA (v_mfma_f32_16x16x4_f32); an output element is one
+ *                         chain over n whose order depends on (N, K) only, never on M or on which rows share the launch: a row's result
+ *                         is bit-identical in any batch and on every run.  A NaN in dy row r reaches out row r only.
+ *   nd_ensemble_xent_bwd  the cross-entropy of the members' AVERAGED probabilities.  logits [K, B, C] fp32 (1 <= K <= 32,
+ *                         2 <= C <= 1024), labels int64 [B]: p_k = softmax(logits_k) (max-subtracted), P[b, c] = (sum_k p_k[b, c]) / K
+ *                         summed in member order k = 0 .. K-1, loss[b] = -logf(P[b, y]), dlogits_k[b, c] = w_k (p_k[b, c] - [c == y]),
+ *                         w_k = p_k[b, y] / sum_j p_j[b, y] (the 1 / K cancels).  Conventions: sum_j p_j[b, y] == 0 (underflow):
+ *                         loss = +inf and dlogits = 0; a NaN logit anywhere in row b (any member): that row's P, loss and dlogits are NaN
+ *                         (sign(NaN) = 0 in nd_linf_step: no step); a label outside [0, C): loss NaN, dlogits 0, P as usual.
+ *                         labels NULL: only P is written (the scores-only call; loss and dlogits may be NULL). */
+#define ND_LINEAR_BWD_MAX_M 128
+int nd_linear_bwd(const float *dy_dev, const void *w_packed_dev, const float *gate_dev, const float *add_dev, float *out_dev, int M, int N,
+                  int K, int dtype, void *stream);
+int nd_ensemble_xent_bwd(const float *logits_dev, const int64_t *labels_dev, float *P_dev, float *loss_dev, float *dlogits_dev, int K, int B,
+                         int C, void *stream);
+
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */
 /* add_noise (:272-279): out = x + z * std, z = the randn_like draw (supplied, like the sampler's noise). */

@@ -1,7 +1,7 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
     python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD --eps E --out ROOT \
-        [--preprocess grayscaled] [--seed S] [--batch_size B]
+        [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner] [--members 0,1,...]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
 test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
@@ -10,6 +10,9 @@ as RGB uint8 = round(255 * adv), with the classes and file stems of the source: 
 AutoAttack(vit, eps=eps, version='custom', norm='Linf', attacks_to_run=['apgd-ce']) run by run_standard_evaluation on each batch.
 A Carlini & Wagner set is written from Python: write_attacked_set(config, attack.CarliniWagner(eps, vit, ...), "CW", out); so is a
 Square set: write_attacked_set(config, square.SquareAttack(vit, eps=eps), "SQUARE", out) (no dataset name reads that tree back).
+--target conditioner attacks the mapping networks the ensemble is conditioned on instead of the full ViT's head (a white-box attack on the
+defence's front end): the checkpoints are read by mapping.load_conditioner and wrapped in a mapping.ConditionerTarget, whose loss is the
+cross-entropy of the members' averaged softmax; --members selects the members (default: all).
 """
 from __future__ import annotations
 
@@ -32,18 +35,38 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--dataroot", type=str, default=None)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--target", type=str, choices=["vit", "conditioner"], default="vit",
+                   help="vit: the full ViT's head, as the reference attacks; conditioner: the mapping networks the ensemble is conditioned on")
+    p.add_argument("--members", type=str, default=None, help="--target conditioner: comma-separated member indices (default: all)")
     return p
+
+
+def parse_members(text):
+    """'0,2' -> [0, 2]; None -> None (all members)"""
+    return None if text is None else [int(t) for t in text.split(",") if t.strip()]
+
+
+def checkpoint_name(config) -> str:
+    """The dataset part of the checkpoint file names the runner would load for the config's dataset."""
+    from .runner import CHEST
+
+    base = config.data.dataset.split("Atk", 1)[0].replace("Validate", "")
+    return "ChestXRay" if base in CHEST else "ISICSkinCancer"
 
 
 def load_vit(config, device):
     """The ViT checkpoint the runner would load for the config's dataset."""
     from .mapping import VisionTransformer, load_pickled
-    from .runner import CHEST
 
-    base = config.data.dataset.split("Atk", 1)[0].replace("Validate", "")
-    ckpt = "ChestXRay" if base in CHEST else "ISICSkinCancer"
-    sd = load_pickled(os.path.join(config.diffusion.trained_aux_cls_ckpt_path, f"vit_base_patch16_224_{ckpt}.pth"))
+    sd = load_pickled(os.path.join(config.diffusion.trained_aux_cls_ckpt_path, f"vit_base_patch16_224_{checkpoint_name(config)}.pth"))
     return VisionTransformer(sd, max(1, sd["patch_embed.proj.weight"].shape[0] // 64), device)
+
+
+def load_target(config, device, members=None):
+    """--target conditioner: the conditioner the runner would load for the config's dataset, as the model of a gradient attack."""
+    from .mapping import ConditionerTarget, load_conditioner
+
+    return ConditionerTarget(load_conditioner(config.diffusion.trained_aux_cls_ckpt_path, checkpoint_name(config), device), members)
 
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
@@ -93,11 +116,13 @@ def main(argv=None) -> int:
     from .autoattack import AutoAttack
 
     args = build_parser().parse_args(argv)
+    if args.target == "vit" and args.members is not None:
+        raise SystemExit("--members selects members of --target conditioner")
     with open(args.config) as f:
         import yaml
         config = nd_main.dict2namespace(yaml.safe_load(f))
     device = torch.device("cuda", args.device)
-    vit = load_vit(config, device)
+    vit = load_vit(config, device) if args.target == "vit" else load_target(config, device, parse_members(args.members))
     if args.attack_name == "AUTOPGD":
         attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
     else:

@@ -58,6 +58,23 @@ class Classifier:
         x = ops.linear(x, p["linear3.weight"], p["linear3.bias"], act="relu")
         return ops.linear(x, p["linear4.weight"], p["linear4.bias"])
 
+    def forward_recorded(self, x: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """forward's launches in forward's order, keeping the three post-ReLU activations input_grad gates with: (logits, [h1, h2, h3])."""
+        p, h, acts = self.p, x.reshape(-1, self.in_features), []
+        for i in (1, 2, 3):
+            h = ops.linear(h, p[f"linear{i}.weight"], p[f"linear{i}.bias"], act="relu")
+            acts.append(h)
+        return ops.linear(h, p["linear4.weight"], p["linear4.bias"]), acts
+
+    def input_grad(self, dlogits: torch.Tensor, acts: List[torch.Tensor], add: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dL/d(the MLP's input) [B, in_features] from dlogits [B, C]: four linear_grad_input calls down the layers, each gated by the
+        activation forward_recorded kept; `add` [B, in_features] joins at the input (the gradient the shared ViT prefix already carries)."""
+        p = self.p
+        d = ops.linear_grad_input(dlogits, p["linear4.weight"], gate=acts[2])
+        d = ops.linear_grad_input(d, p["linear3.weight"], gate=acts[1])
+        d = ops.linear_grad_input(d, p["linear2.weight"], gate=acts[0])
+        return ops.linear_grad_input(d, p["linear1.weight"], add=add)
+
 
 class VisionTransformer:
     """The subset of timm 0.4.12 VisionTransformer the path touches, over a timm state_dict."""
@@ -344,6 +361,80 @@ class GuidingConditioner:
         if side_stream is not None:
             main.wait_stream(side_stream)
         return out
+
+    # ---- input gradient of the mapping networks themselves (the white-box attacks on the defence's front end) ---------------------------
+    def _members(self, members) -> List[int]:
+        members = list(range(len(self.mlps))) if members is None else [int(m) for m in members]
+        if not members or len(set(members)) != len(members) or min(members) < 0 or max(members) >= len(self.mlps):
+            raise ValueError(f"members must be distinct indices in [0, {len(self.mlps)}), at least one (got {members})")
+        return members
+
+    def input_grad(self, x: torch.Tensor, labels: torch.Tensor, members: Optional[Sequence[int]] = None, check_labels: bool = True):
+        """(P, dx, loss, logits) of the members the ensemble is conditioned on (member k: patch_embed -> blocks[0..k] -> mlps[k] -> softmax):
+        P [B, C] = the selected members' averaged softmax, loss [B] = -log P[b, label], dx = d(loss.sum()) / dx [B, 3, H, W], logits
+        [len(members), B, C] in the order of `members` (default: all).  The forward is compute_guiding_prediction_py's launches in its order
+        (the logits equal compute_guiding_prediction's bit for bit); the backward is ONE chain down the shared prefix from the deepest
+        selected member: each member's dlogits go through its MLP (Classifier.input_grad) and join the running token gradient at its
+        level before that level's block gradient.  fp32 (split) form only.  After the optional label check nothing is read back."""
+        vit = self.vit
+        members = self._members(members)
+        x = ops._f32(x, "x")
+        if x.dim() != 4:
+            raise ValueError("x must be [B, C, H, W]")
+        B, _, H, W = x.shape
+        n_tok = (H // vit.patch) * (W // vit.patch)
+        if n_tok > ops.ATTENTION_BWD_MAX_TOKENS:
+            raise _lib.NdError(f"input_grad: the attention backward takes N <= {ops.ATTENTION_BWD_MAX_TOKENS} tokens per image (N={n_tok})")
+        if any(m.p["linear1.weight"].dtype != _lib.ND_DTYPE_F32 for m in self.mlps):
+            raise _lib.NdError("input_grad runs in the default fp32 (split) form only: the mapping MLPs hold fp16 images")
+        wT = vit.transposed_weights()                      # refuses fp16 mode and ND_GEMM_F32=mfma_f32
+        top = max(members)
+        tok, recs, heads = vit.patch_embed(x), [], {}
+        for i in range(top + 1):
+            recs.append({})
+            tok = vit.block(i, tok, B, rec=recs[-1])
+            if i in members:
+                heads[i] = self.mlps[i].forward_recorded(tok)
+        logits = torch.stack([heads[m][0] for m in members])
+        P, loss, dlogits = ops.ensemble_xent_grad(logits, labels, check_labels=check_labels)
+        dtok, dimg = None, None
+        for i in range(top, -1, -1):
+            if i in heads:
+                add = dtok.reshape(B, -1) if dtok is not None else None
+                dtok = self.mlps[i].input_grad(dlogits[members.index(i)], heads.pop(i)[1], add=add).reshape(B * n_tok, vit.embed_dim)
+                dimg = ops.split_rows(dtok)
+            dtok, dimg = vit._block_grad(i, recs[i], dtok, dimg, B)
+            recs[i] = None
+        dcols = ops.gemm_split(dimg, wT["patch_embed"])
+        return P, ops.unpatchify(dcols, B, vit.in_chans, H, W, vit.patch), loss, logits
+
+
+class ConditionerTarget:
+    """What the gradient attacks take as their model when the mapping networks themselves are attacked: .device, forward(x) -> the
+    selected members' averaged softmax P [B, C] (scores; the attacks use only their argmax) and input_grad(x, labels) -> (P, dx, loss).
+    It deliberately has no attribute called `vit`: attack._vit would unwrap it and attack the full ViT's head instead."""
+
+    def __init__(self, cond: GuidingConditioner, members: Optional[Sequence[int]] = None):
+        self.cond = cond
+        self.members = None if members is None else cond._members(members)
+        self.device = cond.vit.device
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """P [B, C]: the C-level compute_guiding_prediction, then the scores-only head call on the selected members.  That one library call
+        runs EVERY member, so a subset still streams all the mapping MLPs' weights in a forward (input_grad stops at max(members))."""
+        out = self.cond.compute_guiding_prediction(x, include_full_vit=False)
+        sel = out if self.members is None else [out[m] for m in self.members]
+        return ops.ensemble_xent_grad(torch.stack(sel))[0]
+
+    __call__ = forward
+
+    def input_grad(self, x: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        P, dx, loss, _ = self.cond.input_grad(x, labels, self.members)
+        return P, dx, loss
+
+    def input_grad_margin(self, *args, **kwargs):
+        raise NotImplementedError("Carlini-Wagner (CarliniWagner) is not implemented on a ConditionerTarget: its margin loss is defined on the "
+                                  "full ViT's logits, not on the members' averaged probabilities")
 
 
 # ---- checkpoint readers (SURVEY section 5 'checkpoint / resume') -----------------------------------

@@ -830,3 +830,66 @@ def cw_update(s: CwState, dx: torch.Tensor, xrec: torch.Tensor, stepsize: float,
     check(_lib.load().nd_cw_update(ptr(s.delta), ptr(s.m), ptr(s.v), ptr(dx), ptr(s.x), ptr(xrec), ptr(s.t), ptr(s.best),
                                    ptr(s.flags) if use_flags else None, s.B, s.per, float(stepsize), bc1, bc2, cw_b_half(lo, hi),
                                    _stream(dx)), "nd_cw_update")
+
+
+# ---- the gradient through the mapping MLPs (include/nested_diffusion.h: nd_linear_bwd, nd_ensemble_xent_bwd; the chain: mapping.py) -----
+LINEAR_BWD_MAX_M = 128                                     # ND_LINEAR_BWD_MAX_M: rows per nd_linear_bwd launch
+
+
+def linear_grad_input(dy: torch.Tensor, weight: PackedWeight, gate: Optional[torch.Tensor] = None,
+                      add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """((dy @ W) * (gate > 0)) + add: the input gradient of linear(x, weight) given dy = dL/d(its output) [M, N], read from the weight's
+    packed image in place (no transposed copy).  gate [M, K]: the forward's post-ReLU input of that Linear (ReLU'(0) = 0), or None;
+    add [M, K]: a gradient that joins at the Linear's input, or None.  More than 128 rows run as chunks of 128 (a row's result does not
+    depend on the rows beside it: the chunks are the bits of one launch)."""
+    lib = _lib.load()
+    if not isinstance(weight, PackedWeight):
+        raise TypeError("weight must be a PackedWeight (the image the forward streams)")
+    if weight.dtype != _lib.ND_DTYPE_F32:
+        raise _lib.NdError("linear_grad_input reads fp32 weight images only: the input gradient runs in fp32 mode, not on an fp16 PackedWeight")
+    dy = _f32(dy, "dy")
+    if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] != weight.N:
+        raise ValueError(f"dy is {tuple(dy.shape)}, weight is [{weight.N}, {weight.K}]: expected [M >= 1, {weight.N}]")
+    M, N, K = dy.shape[0], weight.N, weight.K
+    if K % 16:
+        raise ValueError(f"K must be a multiple of 16 (K={K})")
+    gate = _f32(gate, "gate") if gate is not None else None
+    add = _f32(add, "add") if add is not None else None
+    for t, name in ((gate, "gate"), (add, "add")):
+        if t is not None and (tuple(t.shape) != (M, K) or t.device != dy.device):
+            raise ValueError(f"{name} is {tuple(t.shape)} on {t.device}; expected [{M}, {K}] on {dy.device}")
+    if weight.data.device != dy.device:
+        raise ValueError(f"weight is on {weight.data.device}, dy on {dy.device}")
+    out = torch.empty(M, K, dtype=torch.float32, device=dy.device)
+    for s in range(0, M, LINEAR_BWD_MAX_M):
+        e = min(s + LINEAR_BWD_MAX_M, M)
+        check(lib.nd_linear_bwd(ptr(dy[s:e]), ptr(weight.data), ptr(gate[s:e]) if gate is not None else None,
+                                ptr(add[s:e]) if add is not None else None, ptr(out[s:e]), e - s, N, K, weight.dtype, _stream(dy)),
+              "nd_linear_bwd")
+    return out
+
+
+def ensemble_xent_grad(logits: torch.Tensor, labels: Optional[torch.Tensor] = None, check_labels: bool = True):
+    """(P [B, C], loss [B], dlogits [K, B, C]) of the cross-entropy of the members' averaged softmax (nd_ensemble_xent_bwd): logits
+    [K, B, C], P = mean_k softmax(logits_k), loss = -log P[b, label], dlogits_k = dloss / dlogits_k.  labels None: (P, None, None), the
+    scores-only call.  check_labels=False skips the label-range check, which reads back (the kernel gives an out-of-range label a NaN loss
+    and no gradient)."""
+    logits = _f32(logits, "logits")
+    if logits.dim() != 3:
+        raise ValueError("logits must be [K, B, C]")
+    K, B, C = logits.shape
+    if not 1 <= K <= 32 or B < 1 or not 2 <= C <= 1024:
+        raise ValueError(f"the ensemble head takes 1 <= K <= 32 members, B >= 1 and 2 <= C <= 1024 classes (K={K}, B={B}, C={C})")
+    P = torch.empty(B, C, dtype=torch.float32, device=logits.device)
+    loss = dlogits = None
+    if labels is not None:
+        labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+        if tuple(labels.shape) != (B,):
+            raise ValueError(f"labels must be [{B}]")
+        if check_labels and (int(labels.min()) < 0 or int(labels.max()) >= C):
+            raise ValueError(f"labels must lie in [0, {C})")
+        loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+        dlogits = torch.empty_like(logits)
+    check(_lib.load().nd_ensemble_xent_bwd(ptr(logits), ptr(labels), ptr(P), ptr(loss), ptr(dlogits), K, B, C, _stream(logits)),
+          "nd_ensemble_xent_bwd")
+    return P, loss, dlogits
