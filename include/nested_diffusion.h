@@ -1,6 +1,8 @@
 /*
  * nested_diffusion.h -- C ABI of libnd_hip.so, the MI355X (gfx950) implementation of the
- * nested-diffusion (LaDiNE) inference hot path.
+ * nested-diffusion (LaDiNE) inference hot path, of the attacks on it, and of the training step of the
+ * mapping MLPs (the weight gradient and Adam fused into one pass over the packed weight: "training of
+ * the mapping MLPs" below).  Training of the noise estimators and of the ViT is not implemented.
  *
  * The reference (xingbpshen/nested-diffusion) has no FFI: its hot path is plain Python calling
  * torch ops.  Each entry point below therefore names the reference Python call(s) it replaces
@@ -619,6 +621,44 @@ int nd_linear_bwd(const float *dy_dev, const void *w_packed_dev, const float *ga
                   int K, int dtype, void *stream);
 int nd_ensemble_xent_bwd(const float *logits_dev, const int64_t *labels_dev, float *P_dev, float *loss_dev, float *dlogits_dev, int K, int B,
                          int C, void *stream);
+
+/* ---- training of the mapping MLPs (csrc/nd_mlp_train.hip; the loop: train_mapping.py MappingTrainer; replaces loss.backward() and
+ * optimizer.step() of mapping/train_mapping.py:114-115 for the four Linear layers of mapping/models/mlp.py).  With nd_linear_bwd and
+ * nd_ensemble_xent_bwd (K = 1: the plain softmax cross-entropy) above, these are the backward pass and torch.optim.Adam of one step.
+ * fp32 data and ND_DTYPE_F32 images only (an ND_DTYPE_F16 image is refused, ND_ERR_ARG).  None of them allocates, copies synchronously or
+ * synchronises; no atomics, no cross-workgroup communication; every loop is bounded by the shape arguments.
+ *   nd_adam_step          what one Adam step needs, formed by the host in double and rounded once: step_size = lr / (1 - beta1^t),
+ *                         sqrt_bc2 = sqrt(1 - beta2^t).
+ *   nd_linear_wgrad_adam  acc[n, k] = sum_m dy[m, n] x[m, k] (exact-f32 MFMA, v_mfma_f32_16x16x4_f32), then torch 1.10's F.adam listing
+ *                         (no weight decay, no amsgrad), one rounded fp32 operation per line, no contraction, correctly rounded division
+ *                         and square root:
+ *                             g = acc * gscale
+ *                             m = (m * beta1) + (g * one_minus_beta1)
+ *                             v = (v * beta2) + ((g * g) * one_minus_beta2)
+ *                             denom = (sqrt(v) / sqrt_bc2) + eps
+ *                             w = w - step_size * (m / denom)
+ *                         dy [M, N], x [M, K] row-major; w / m / v / g_out: nd_pack_rows images of [N, K] matrices, distinct buffers,
+ *                         updated in place.  1 <= M <= ND_LINEAR_BWD_MAX_M, K % 16 == 0, N >= 1.  a == NULL: only g_out is written
+ *                         (w / m / v may be NULL); g_out == NULL: no gradient is written; both NULL: ND_ERR_ARG.  Rows of dy / x past M
+ *                         are zero-filled in registers, never read; image rows N .. 16 * ceil(N / 16) have gradient exactly 0 and are not
+ *                         updated: they stay exactly 0 in w, m, v whatever the step holds (eps = 0 included).  A workgroup owns a range of 16-column blocks, keeps their x fragments in registers and
+ *                         walks a range of row blocks: every 16 x 16 block is read and written by exactly one wave, once, and its
+ *                         result does not depend on the launch geometry: race-free in place, the same bits on every run.  A NaN in dy
+ *                         column n / x column k reaches only weight row n / column k.
+ *   nd_linear_wgrad_plan  the launch geometry of that kernel for an [N, K] weight: out[0] = 16-column blocks per workgroup,
+ *                         out[1] = workgroups over K, out[2] = workgroups over the row blocks, out[3] = row blocks per workgroup
+ *                         (tests pick their shapes and sampled blocks from it).  No GPU needed.
+ *   nd_bias_grad_adam     acc[n] = sum_m dy[m, n] in the order m = 0 .. M - 1, then the same listing on b, m, v [N] (g_out [N] or NULL).
+ *   nd_unpack_rows        the exact inverse of nd_pack_rows for an ND_DTYPE_F32 image: dst [R, K] row-major, padding rows dropped. */
+typedef struct nd_adam_step {
+    float beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bc2, eps;
+} nd_adam_step;
+int nd_linear_wgrad_adam(const float *dy_dev, const float *x_dev, void *w_packed_dev, void *m_packed_dev, void *v_packed_dev,
+                         void *g_out_packed_dev, int M, int N, int K, int dtype, float gscale, const nd_adam_step *a, void *stream);
+int nd_linear_wgrad_plan(int N, int K, int *out4);
+int nd_bias_grad_adam(const float *dy_dev, float *b_dev, float *m_dev, float *v_dev, float *g_out_dev, int M, int N, float gscale,
+                      const nd_adam_step *a, void *stream);
+int nd_unpack_rows(const void *src_packed_dev, float *dst_dev, int R, int K, int dtype, void *stream);
 
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */

@@ -83,6 +83,11 @@ class NdMlpWeights(C.Structure):
     _fields_ = [("w_packed", C.c_void_p * 4), ("bias", C.c_void_p * 4)]
 
 
+class NdAdamStep(C.Structure):
+    """nd_adam_step: one Adam step's constants, rounded once from double (ops.adam_step)"""
+    _fields_ = [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "step_size", "sqrt_bc2", "eps")]
+
+
 class NdBatchOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("samples", "prob", "vote", "probs", "yhat")]
 
@@ -182,6 +187,10 @@ SIGNATURES = {
     "nd_cw_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _vp]),
     "nd_linear_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nd_ensemble_xent_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_linear_wgrad_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, C.POINTER(NdAdamStep), _vp]),
+    "nd_linear_wgrad_plan": (_i, [_i, _i, C.POINTER(_i)]),
+    "nd_bias_grad_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.POINTER(NdAdamStep), _vp]),
+    "nd_unpack_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
 }
 

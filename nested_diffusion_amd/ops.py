@@ -53,6 +53,20 @@ class PackedWeight:
         self.data = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
         check(lib.nd_pack_rows(ptr(weight), ptr(self.data), self.N, self.K, self.dtype, _stream(weight)), "nd_pack_rows")
 
+    def unpack(self) -> torch.Tensor:
+        """The row-major [N, K] weight back out of an fp32 image (nd_unpack_rows: the exact inverse of the packing, padding rows dropped)."""
+        if self.dtype != _lib.ND_DTYPE_F32:
+            raise _lib.NdError("unpack reads fp32 weight images only: an fp16 PackedWeight does not hold the fp32 weight")
+        out = torch.empty(self.N, self.K, dtype=torch.float32, device=self.data.device)
+        check(_lib.load().nd_unpack_rows(ptr(self.data), ptr(out), self.N, self.K, self.dtype, _stream(self.data)), "nd_unpack_rows")
+        return out
+
+    def zeros_like(self) -> "PackedWeight":
+        """An image of the same shape and dtype, all zero (Adam's m and v)."""
+        z = object.__new__(PackedWeight)
+        z.N, z.K, z.dtype, z.data = self.N, self.K, self.dtype, torch.zeros_like(self.data)
+        return z
+
 
 def linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, act=None,
            scale: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -893,3 +907,100 @@ def ensemble_xent_grad(logits: torch.Tensor, labels: Optional[torch.Tensor] = No
     check(_lib.load().nd_ensemble_xent_bwd(ptr(logits), ptr(labels), ptr(P), ptr(loss), ptr(dlogits), K, B, C, _stream(logits)),
           "nd_ensemble_xent_bwd")
     return P, loss, dlogits
+
+
+def adam_step(lr: float, t: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8) -> "_lib.NdAdamStep":
+    """nd_adam_step of step t >= 1 (torch.optim.Adam's `step` after its increment): the bias corrections are formed in double, as torch's
+    Python does, and every field is rounded to fp32 once: step_size = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t)."""
+    t = int(t)
+    if t < 1:
+        raise ValueError(f"Adam steps count from 1 (t={t})")
+    b1, b2 = float(betas[0]), float(betas[1])
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or lr < 0.0 or eps < 0.0:
+        raise ValueError(f"adam_step needs lr >= 0, eps >= 0 and betas in [0, 1) (lr={lr}, betas={betas}, eps={eps})")
+    return _lib.NdAdamStep(b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, float(eps))
+
+
+def _adam_images(weight: PackedWeight, m, v, adam, return_grad: bool, what: str):
+    if adam is None:
+        if not return_grad:
+            raise ValueError(f"{what}: adam=None and return_grad=False: nothing to compute")
+        return
+    if not isinstance(adam, _lib.NdAdamStep):
+        raise TypeError("adam must be an ops.adam_step(...) or None")
+    for img, name in ((m, "m"), (v, "v")):
+        if not isinstance(img, PackedWeight):
+            raise TypeError(f"{name} must be a PackedWeight (weight.zeros_like())")
+        if (img.N, img.K, img.dtype) != (weight.N, weight.K, weight.dtype) or img.data.device != weight.data.device:
+            raise ValueError(f"{name} is a [{img.N}, {img.K}] image on {img.data.device}; expected weight's [{weight.N}, {weight.K}] on "
+                             f"{weight.data.device}")
+    if len({weight.data.data_ptr(), m.data.data_ptr(), v.data.data_ptr()}) != 3:
+        raise ValueError("weight, m and v must be distinct images")
+
+
+def linear_wgrad_adam(dy: torch.Tensor, x: torch.Tensor, weight: PackedWeight, m: Optional[PackedWeight], v: Optional[PackedWeight], adam,
+                      gscale: float = 1.0, return_grad: bool = False) -> Optional[PackedWeight]:
+    """One Adam step of linear(x, weight)'s weight on the gradient gscale * (dy^T @ x), dy = dL/d(its output) [M, N], x its input [M, K]
+    (nd_linear_wgrad_adam: the gradient is formed tile by tile and applied in registers, never written unless asked for).  weight, m, v
+    are updated IN PLACE in their packed images: weight.data keeps its address, so whatever streams that image sees the new weights.
+    adam: ops.adam_step(lr, t), or None for the gradient-only call (m, v unused).  return_grad: also return the gradient as a packed
+    image (.unpack() gives [N, K]).  1 <= M <= 128."""
+    lib = _lib.load()
+    if not isinstance(weight, PackedWeight):
+        raise TypeError("weight must be a PackedWeight (the image the forward streams)")
+    if weight.dtype != _lib.ND_DTYPE_F32:
+        raise _lib.NdError("linear_wgrad_adam updates fp32 weight images only: training runs in fp32 mode, not on an fp16 PackedWeight")
+    dy, x = _f32(dy, "dy"), _f32(x, "x")
+    if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] != weight.N:
+        raise ValueError(f"dy is {tuple(dy.shape)}, weight is [{weight.N}, {weight.K}]: expected [M >= 1, {weight.N}]")
+    M, N, K = dy.shape[0], weight.N, weight.K
+    if M > LINEAR_BWD_MAX_M:
+        raise ValueError(f"linear_wgrad_adam takes at most {LINEAR_BWD_MAX_M} rows per step (M={M}): a weight gradient sums over the batch, "
+                         f"it cannot run as chunks")
+    if K % 16:
+        raise ValueError(f"K must be a multiple of 16 (K={K})")
+    if tuple(x.shape) != (M, K) or x.device != dy.device:
+        raise ValueError(f"x is {tuple(x.shape)} on {x.device}; expected [{M}, {K}] on {dy.device}")
+    if weight.data.device != dy.device:
+        raise ValueError(f"weight is on {weight.data.device}, dy on {dy.device}")
+    _adam_images(weight, m, v, adam, return_grad, "linear_wgrad_adam")
+    g = weight.zeros_like() if return_grad else None
+    check(lib.nd_linear_wgrad_adam(ptr(dy), ptr(x), ptr(weight.data), ptr(m.data) if adam is not None else None,
+                                   ptr(v.data) if adam is not None else None, ptr(g.data) if g is not None else None, M, N, K, weight.dtype,
+                                   float(gscale), ctypes.byref(adam) if adam is not None else None, _stream(dy)), "nd_linear_wgrad_adam")
+    return g
+
+
+def linear_wgrad_plan(N: int, K: int) -> dict:
+    """The launch geometry of nd_linear_wgrad_adam for an [N, K] weight (host only): 16-column blocks per workgroup, workgroups over K,
+    workgroups over the row blocks, row blocks per workgroup."""
+    out = (ctypes.c_int * 4)()
+    check(_lib.load().nd_linear_wgrad_plan(int(N), int(K), out), "nd_linear_wgrad_plan")
+    return {"kb_per_wg": out[0], "grid_x": out[1], "grid_y": out[2], "rb_per_wg": out[3]}
+
+
+def bias_grad_adam(dy: torch.Tensor, bias: torch.Tensor, m: Optional[torch.Tensor], v: Optional[torch.Tensor], adam, gscale: float = 1.0,
+                   return_grad: bool = False) -> Optional[torch.Tensor]:
+    """One Adam step of a bias [N] on the gradient gscale * dy.sum(0) (summed in the order m = 0 .. M - 1), in place (nd_bias_grad_adam).
+    adam None: the gradient-only call."""
+    dy = _f32(dy, "dy")
+    if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] < 1:
+        raise ValueError(f"dy is {tuple(dy.shape)}: expected [M >= 1, N >= 1]")
+    M, N = dy.shape
+    if adam is None:
+        if not return_grad:
+            raise ValueError("bias_grad_adam: adam=None and return_grad=False: nothing to compute")
+    else:
+        if not isinstance(adam, _lib.NdAdamStep):
+            raise TypeError("adam must be an ops.adam_step(...) or None")
+        for t, name in ((bias, "bias"), (m, "m"), (v, "v")):
+            _inplace(t, name, shape=(N,))
+            if t.device != dy.device:
+                raise ValueError(f"{name} is on {t.device}, dy on {dy.device}")
+        if len({bias.data_ptr(), m.data_ptr(), v.data_ptr()}) != 3:
+            raise ValueError("bias, m and v must be distinct tensors")
+    g = torch.empty(N, dtype=torch.float32, device=dy.device) if return_grad else None
+    on = adam is not None
+    check(_lib.load().nd_bias_grad_adam(ptr(dy), ptr(bias) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N,
+                                        float(gscale), ctypes.byref(adam) if on else None, _stream(dy)), "nd_bias_grad_adam")
+    return g
