@@ -612,8 +612,13 @@ int nd_cw_update(float *delta_dev, float *m_dev, float *v_dev, const float *dx_d
  *   nd_ensemble_xent_bwd  the cross-entropy of the members' AVERAGED probabilities.  logits [K, B, C] fp32 (1 <= K <= 32,
  *                         2 <= C <= 1024), labels int64 [B]: p_k = softmax(logits_k) (max-subtracted), P[b, c] = (sum_k p_k[b, c]) / K
  *                         summed in member order k = 0 .. K-1, loss[b] = -logf(P[b, y]), dlogits_k[b, c] = w_k (p_k[b, c] - [c == y]),
- *                         w_k = p_k[b, y] / sum_j p_j[b, y] (the 1 / K cancels).  Conventions: sum_j p_j[b, y] == 0 (underflow):
- *                         loss = +inf and dlogits = 0; a NaN logit anywhere in row b (any member): that row's P, loss and dlogits are NaN
+ *                         w_k = p_k[b, y] / sum_j p_j[b, y] (the 1 / K cancels).  K == 1 is the plain softmax cross-entropy and is
+ *                         formed as a log-softmax, as nn.CrossEntropyLoss is: loss[b] = logf(sum_c exp(l_c - max)) - (l_y - max),
+ *                         dlogits[b, c] = p[b, c] - [c == y], no division by p[b, y]: it never reports underflow (a label that trails
+ *                         the leading logit by more than 104 gives loss = that margin and dlogits = -1 at the label).  Conventions:
+ *                         K >= 2 and sum_j p_j[b, y] == 0 (every member underflows at the label): loss = +inf and dlogits = 0 (a member
+ *                         that underflows alone has w_k = 0 exactly, the others share the gradient); a NaN logit anywhere in row b (any
+ *                         member; a largest logit of +inf and an all -inf row are such rows): that row's P, loss and dlogits are NaN
  *                         (sign(NaN) = 0 in nd_linf_step: no step); a label outside [0, C): loss NaN, dlogits 0, P as usual.
  *                         labels NULL: only P is written (the scores-only call; loss and dlogits may be NULL). */
 #define ND_LINEAR_BWD_MAX_M 128
@@ -624,14 +629,15 @@ int nd_ensemble_xent_bwd(const float *logits_dev, const int64_t *labels_dev, flo
 
 /* ---- training of the mapping MLPs (csrc/nd_mlp_train.hip; the loop: train_mapping.py MappingTrainer; replaces loss.backward() and
  * optimizer.step() of mapping/train_mapping.py:114-115 for the four Linear layers of mapping/models/mlp.py).  With nd_linear_bwd and
- * nd_ensemble_xent_bwd (K = 1: the plain softmax cross-entropy) above, these are the backward pass and torch.optim.Adam of one step.
+ * nd_ensemble_xent_bwd (K = 1: the plain softmax cross-entropy, a log-softmax that is exact at any margin) above, these are the backward pass and torch.optim.Adam of one step.
  * fp32 data and ND_DTYPE_F32 images only (an ND_DTYPE_F16 image is refused, ND_ERR_ARG).  None of them allocates, copies synchronously or
  * synchronises; no atomics, no cross-workgroup communication; every loop is bounded by the shape arguments.
  *   nd_adam_step          what one Adam step needs, formed by the host in double and rounded once: step_size = lr / (1 - beta1^t),
  *                         sqrt_bc2 = sqrt(1 - beta2^t).
  *   nd_linear_wgrad_adam  acc[n, k] = sum_m dy[m, n] x[m, k] (exact-f32 MFMA, v_mfma_f32_16x16x4_f32), then torch 1.10's F.adam listing
  *                         (no weight decay, no amsgrad), one rounded fp32 operation per line, no contraction, correctly rounded division
- *                         and square root:
+ *                         and square root, on every fp32 input: denormals are kept (operands of the MFMA, g, g * g, m and v alike), signed
+ *                         zeros, infinities and NaN follow IEEE 754 (a zero acc is +0: the contraction starts from +0):
  *                             g = acc * gscale
  *                             m = (m * beta1) + (g * one_minus_beta1)
  *                             v = (v * beta2) + ((g * g) * one_minus_beta2)

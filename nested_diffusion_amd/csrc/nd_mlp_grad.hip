@@ -153,6 +153,10 @@ void lb_launch(bool vec, dim3 grid, hipStream_t st, const float* dy, const float
 // and sum_c exp(l - max), lanes in stride-64 order folded by an xor butterfly; a NaN logit makes the member's sum, hence the whole row, NaN.
 // Then every thread forms p_k[b, c] = exp(l - max_k) / sum_k for its columns, P = (sum_k p_k) / K in member order, and with labels
 // S = sum_k p_k[b, y] in member order, loss = -logf(S / K) (the bits of -logf(P[b, y])) and dlogits_k = (p_k[b, y] / S) (p_k - [c == y]).
+// One member (K == 1) is the plain softmax cross-entropy and is formed as a log-softmax, as torch's nn.CrossEntropyLoss is:
+// loss = logf(sum) - (l_y - max) and dlogits = p - [c == y], no division by S.  p[b, y] may underflow there (a confidently wrong
+// training sample, the label 104 or more behind the leading logit): the loss is then the margin and the gradient at the label -1, not
+// +inf and 0 -- the S == 0 convention below is the ensemble's (K >= 2) alone.
 // ---------------------------------------------------------------------------------------------
 constexpr int EX_MAXK = 32;
 
@@ -183,14 +187,16 @@ __global__ __launch_bounds__(256) void k_ensemble_xent_bwd(const float* __restri
     float S = 0.f;
     if (have && valid)
         for (int k = 0; k < K; ++k) S += s_py[k];
-    if (have && t == 0) loss[b] = valid ? -logf(S / (float)K) : NAN;
-    const bool live = have && valid && S != 0.f;           // S == 0 (underflow): loss = +inf above, no gradient; S NaN: NaN everywhere
+    const bool one = K == 1;                               // the plain cross-entropy: a log-softmax, which has no underflow to report
+    if (have && t == 0) loss[b] = !valid ? NAN : one ? logf(s_sum[0]) - (lb[y] - s_mx[0]) : -logf(S / (float)K);
+    const bool live = have && valid && (one || S != 0.f);  // K >= 2, S == 0 (underflow): loss = +inf above, no gradient; S NaN: NaN everywhere
     for (int c = t; c < C; c += 256) {
         float ps = 0.f;
         for (int k = 0; k < K; ++k) {
             const float p = expf(lb[(size_t)k * kstride + c] - s_mx[k]) / s_sum[k];
             ps += p;
-            if (have) dlogits[(size_t)k * kstride + (size_t)b * C + c] = live ? (s_py[k] / S) * (p - (c == y ? 1.0f : 0.0f)) : 0.f;
+            const float d = p - (c == y ? 1.0f : 0.0f);
+            if (have) dlogits[(size_t)k * kstride + (size_t)b * C + c] = !live ? 0.f : one ? d : (s_py[k] / S) * d;
         }
         P[(size_t)b * C + c] = ps / (float)K;
     }

@@ -22,8 +22,8 @@
 #include "nd_common.hpp"
 #include "../../include/nested_diffusion.h"
 
-// every operation of the update is one rounded fp32 op in the listed order (division and square root correctly rounded): a float32
-// restatement on the host reproduces it bit for bit
+// every operation of the update is one rounded fp32 op in the listed order (division and square root correctly rounded, denormals kept):
+// a float32 restatement on the host reproduces it bit for bit on every input, the edges of fp32 included (tests/test_gpu_mlp_edges.py)
 #pragma clang fp contract(off)
 
 int nd_set_err(int code, const char* fmt, ...);

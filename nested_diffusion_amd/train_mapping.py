@@ -2,7 +2,7 @@
 
 The ViT prefix (patch_embed + blocks[0..mn_idx]) is frozen and runs forward only; the four-layer Classifier on top of it is trained with
 cross-entropy (mean over the batch), torch.optim.Adam's update and StepLR.  One step is: the prefix, Classifier.forward_recorded, the
-softmax cross-entropy head (nd_ensemble_xent_bwd with one member), three nd_linear_bwd calls for the hidden gradients, and then -- only
+softmax cross-entropy head (nd_ensemble_xent_bwd with one member: a log-softmax), three nd_linear_bwd calls for the hidden gradients, and then -- only
 after every gradient that reads a weight has been formed -- one nd_linear_wgrad_adam and one nd_bias_grad_adam per layer, which form the
 weight gradient tile by tile and apply Adam to the packed images in place.  No gradient matrix, no unpacked weight and no autograd graph
 exists at any point; nothing is read back inside a step.

@@ -96,8 +96,12 @@ def ensemble_head_f32(logits: torch.Tensor, labels: torch.Tensor):
     S = torch.zeros(B)
     for k in range(K):
         S = S + py[k]
-    loss = -torch.log(S / K)
     onehot = torch.nn.functional.one_hot(labels, C).float()
+    if K == 1:                                             # the plain cross-entropy, a log-softmax: no division by p_y, no underflow to report
+        mx = logits[0].max(dim=1).values
+        loss = torch.log(e[0].sum(dim=1)) - (logits[0, torch.arange(B), labels] - mx)
+        return P, loss, p - onehot
+    loss = -torch.log(S / K)
     return P, loss, (py / S)[:, :, None] * (p - onehot)
 
 
@@ -119,3 +123,39 @@ def test_ensemble_head_closed_form_agrees_with_float64_autograd(K, C):
     py = p64[:, torch.arange(B), labels]
     d64 = (py / py.sum(0))[:, :, None] * (p64 - torch.nn.functional.one_hot(labels, C).double())
     assert float((d64 - l64.grad).abs().max()) <= 1e-14
+
+
+@pytest.mark.parametrize("C", [2, 10, 1000])
+@pytest.mark.parametrize("margin", [0, 5, 15, 20, 40, 80, 90, 103, 110])
+def test_one_member_is_torch_cross_entropy_at_confident_logits(margin, C):
+    """K = 1 (the trainer's loss head) on rows that lead with the label by `margin` and rows where another class leads it by `margin`: the
+    float32 restatement stays within 4 * 2^-24 * max(1, max |logit|) of float64 F.cross_entropy and within a few ulps of p (of 1 at the
+    label) of softmax - onehot (torch's float32, and float64 once the shared rounding of l - max is counted), past the margin of 104 where exp(l_y - max) is 0 in fp32 -- there the loss is the margin and the gradient at
+    the label -1.  The ensemble form -log(p_y), (p_y / p_y) (p - onehot) gives +inf and 0 / 0 there."""
+    B, U24 = 16, 2.0 ** -24
+    g = torch.Generator().manual_seed(margin * 100 + C)
+    logits = 8 + 0.5 * torch.randn(B, C, generator=g)
+    labels = torch.randint(0, C, (B,), generator=g)
+    rows = torch.arange(B)
+    logits[rows[: B // 2], labels[: B // 2]] = (logits.max(1).values + margin)[: B // 2]
+    other = (labels[B // 2:] + 1) % C
+    logits[rows[B // 2:], other] = logits[rows[B // 2:], labels[B // 2:]] + margin
+    _, loss, d = ensemble_head_f32(logits[None], labels)
+    l64 = logits.double()
+    onehot = torch.nn.functional.one_hot(labels, C).double()
+    p64 = torch.softmax(l64, 1)
+    want = torch.nn.functional.cross_entropy(l64, labels, reduction="none")
+    assert bool(((loss.double() - want).abs() <= 4 * U24 * l64.abs().max(1).values.clamp(min=1)).all())
+    # the elementwise bound of test_xent_head_grad_confident_logits, against torch's float32 softmax as there; against float64 the rounding of
+    # l_c - max (|l_c - max| 2^-24, relative in p_c), which every fp32 softmax shares, joins it
+    p32 = torch.softmax(logits, 1).double()
+    ulps = 2 * (-(-C // 64) + 8) * U24 * (p32 + onehot) + 2.0 ** -126
+    assert bool(((d[0].double() - (p32 - onehot)).abs() <= ulps).all())
+    arg = (l64 - l64.max(1, keepdim=True).values).abs() * U24 * p64
+    assert bool(((d[0].double() - (p64 - onehot)).abs() <= ulps + arg).all())
+    if margin >= 103:
+        wrong = rows[B // 2:]
+        assert bool(((loss[wrong].double() - margin).abs() <= 2.0 ** -15).all()) and bool((d[0, wrong, labels[wrong]] == -1).all())
+        e_y = torch.exp(logits[wrong, labels[wrong]] - logits[wrong].max(1).values)
+        if margin >= 110:
+            assert bool((e_y == 0).all())                  # what the ensemble form divides by
