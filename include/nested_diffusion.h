@@ -1,8 +1,8 @@
 /*
  * nested_diffusion.h -- C ABI of libnd_hip.so, the MI355X (gfx950) implementation of the
- * nested-diffusion (LaDiNE) inference hot path, of the attacks on it, and of the training step of the
- * mapping MLPs (the weight gradient and Adam fused into one pass over the packed weight: "training of
- * the mapping MLPs" below).  Training of the noise estimators and of the ViT is not implemented.
+ * nested-diffusion (LaDiNE) inference hot path, of the attacks on it, and of the training steps of the
+ * mapping MLPs and of the ViT (the weight gradient and Adam / AdamW fused into one pass over the weight:
+ * "training of the mapping MLPs" and "training of the ViT" below).  Training of the noise estimators is not implemented.
  *
  * The reference (xingbpshen/nested-diffusion) has no FFI: its hot path is plain Python calling
  * torch ops.  Each entry point below therefore names the reference Python call(s) it replaces
@@ -665,6 +665,59 @@ int nd_linear_wgrad_plan(int N, int K, int *out4);
 int nd_bias_grad_adam(const float *dy_dev, float *b_dev, float *m_dev, float *v_dev, float *g_out_dev, int M, int N, float gscale,
                       const nd_adam_step *a, void *stream);
 int nd_unpack_rows(const void *src_packed_dev, float *dst_dev, int R, int K, int dtype, void *stream);
+
+/* ---- training of the ViT (csrc/nd_vit_train.hip; the loop: train_transformer.py ViTTrainer; replaces loss.backward() and
+ * optimizer.step() of mapping/train_transformer.py:123-124 for every parameter of timm's vit_base_patch16_224).  The gradients at the
+ * activations come from the input-gradient chain above (nd_layernorm_bwd, nd_gelu_bwd_split, nd_attention_bwd, nd_gemm_split on W^T);
+ * these three form the gradients at the PARAMETERS and apply torch.optim.AdamW.  fp32 row-major data only.  None of them allocates,
+ * copies synchronously or synchronises (they are capturable); no atomics, no split of a contraction over workgroups; every loop is
+ * bounded by the shape arguments; the same bits on every run and under any launch geometry.  They differentiate the SUM of the
+ * per-image losses (as the chain above does): gscale = 1 / B gives nn.CrossEntropyLoss's mean.  Each has a gradient-only mode
+ * (a == NULL: only g_out is written, the parameter and moment pointers may be NULL) and a fused mode (g_out may be NULL); both NULL:
+ * ND_ERR_ARG.  In fused mode the parameter, its moments and g_out are distinct buffers.
+ *   nd_adamw_step             nd_adam_step's fields plus decay = 1 - lr * weight_decay, all formed by the host in double and rounded
+ *                             once.  The update is torch 1.10's F.adamw listing (no amsgrad), one rounded fp32 operation per line, no
+ *                             contraction, correctly rounded division and square root:
+ *                                 g = acc * gscale
+ *                                 w = w * decay
+ *                                 m = (m * beta1) + (g * one_minus_beta1)
+ *                                 v = (v * beta2) + ((g * g) * one_minus_beta2)
+ *                                 denom = (sqrt(v) / sqrt_bc2) + eps
+ *                                 w = w - step_size * (m / denom)
+ *   nd_gemm_tn_adamw          acc[n, k] = sum_m dy[m, n] x[m, k] (exact-f32 MFMA, v_mfma_f32_16x16x4_f32), then the listing on the
+ *                             row-major w, m, v [N, K] in place (g_out [N, K] or NULL).  dy [M, N], x [M, K] row-major, read in the
+ *                             lane layout the instruction wants (no transpose).  M >= 1 (thousands of rows: a workgroup owns one tile
+ *                             of the result and walks M through LDS stages), N >= 1, K % 16 == 0.  Each element is ONE fma chain over
+ *                             m = 0 .. M - 1 carried through every stage: its bits depend on (M, dy, x) alone.  Rows past M and tile
+ *                             rows / columns past N / K are zero operands in registers, never read and never written.
+ *   nd_gemm_tn_plan           the tile geometry of that kernel for an [N, K] result: out[0] = tile rows (over N), out[1] = tile columns
+ *                             (over K), out[2] = rows of M per LDS stage, out[3] = workgroups over K, out[4] = workgroups over N; tile
+ *                             (by, bx) covers rows [by * out[0], ...) x columns [bx * out[1], ...).  No GPU needed.
+ *   nd_colsum_adamw           acc[n] = sum_m dy[m, n], then the listing on b, m, v [N] (g_out [N] or NULL): biases, pos_embed (dy viewed
+ *                             as [B, tokens * E]) and cls_token.  Summation order, a function of M alone: the rows are cut into chunks
+ *                             of ND_COLSUM_CHUNK (the last one shorter); a chunk's partial is p = 0, p += dy[r, n] in row order; the
+ *                             result is acc = 0, acc += p in chunk order.
+ *   nd_layernorm_wgrad_adamw  dgamma[c] = sum_r g[r, c] xhat[r, c], dbeta[c] = sum_r g[r, c] for y = xhat * gamma + beta, g = dL/dy,
+ *                             then the listing on gamma and beta with their moments.  xhat = ((x - mean) - cm) * rstd is recomputed
+ *                             from x exactly as nd_layernorm / nd_layernorm_bwd compute it; dim % 4 == 0, 4 <= dim <= 2048.  The same
+ *                             chunked order over the rows (each product rounded before it is added).  A row's statistics need the
+ *                             whole row, so the work is cut over the rows, not the columns: one wave per chunk writes the chunk's
+ *                             partials to ws_dev (caller-owned, nd_layernorm_wgrad_workspace_bytes(rows, dim) bytes, 16-byte aligned,
+ *                             overwritten; too small: ND_ERR_ARG), a second launch adds them in chunk order and updates.
+ *   nd_layernorm_wgrad_workspace_bytes   2 * dim floats per chunk; 0 for a shape the entry point refuses.  No GPU needed. */
+#define ND_COLSUM_CHUNK 64
+typedef struct nd_adamw_step {
+    float beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bc2, eps, decay;
+} nd_adamw_step;
+int nd_gemm_tn_adamw(const float *dy_dev, const float *x_dev, float *w_dev, float *m_dev, float *v_dev, float *g_out_dev, int M, int N, int K,
+                     float gscale, const nd_adamw_step *a, void *stream);
+int nd_gemm_tn_plan(int N, int K, int *out5);
+int nd_colsum_adamw(const float *dy_dev, float *b_dev, float *m_dev, float *v_dev, float *g_out_dev, int M, int N, float gscale,
+                    const nd_adamw_step *a, void *stream);
+int nd_layernorm_wgrad_adamw(const float *x_dev, const float *g_dev, float *gamma_dev, float *beta_dev, float *m_gamma_dev, float *v_gamma_dev,
+                             float *m_beta_dev, float *v_beta_dev, float *g_out_gamma_dev, float *g_out_beta_dev, int rows, int dim, float eps,
+                             float gscale, const nd_adamw_step *a, void *ws_dev, size_t ws_bytes, void *stream);
+size_t nd_layernorm_wgrad_workspace_bytes(int rows, int dim);
 
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */

@@ -88,6 +88,11 @@ class NdAdamStep(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "step_size", "sqrt_bc2", "eps")]
 
 
+class NdAdamwStep(C.Structure):
+    """nd_adamw_step: one AdamW step's constants, rounded once from double (ops.adamw_step)"""
+    _fields_ = [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "step_size", "sqrt_bc2", "eps", "decay")]
+
+
 class NdBatchOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("samples", "prob", "vote", "probs", "yhat")]
 
@@ -191,6 +196,11 @@ SIGNATURES = {
     "nd_linear_wgrad_plan": (_i, [_i, _i, C.POINTER(_i)]),
     "nd_bias_grad_adam": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.POINTER(NdAdamStep), _vp]),
     "nd_unpack_rows": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "nd_gemm_tn_adamw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(NdAdamwStep), _vp]),
+    "nd_gemm_tn_plan": (_i, [_i, _i, C.POINTER(_i)]),
+    "nd_colsum_adamw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.POINTER(NdAdamwStep), _vp]),
+    "nd_layernorm_wgrad_adamw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, C.POINTER(NdAdamwStep), _vp, _sz, _vp]),
+    "nd_layernorm_wgrad_workspace_bytes": (_sz, [_i, _i]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
 }
 

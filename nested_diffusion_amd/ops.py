@@ -1004,3 +1004,107 @@ def bias_grad_adam(dy: torch.Tensor, bias: torch.Tensor, m: Optional[torch.Tenso
     check(_lib.load().nd_bias_grad_adam(ptr(dy), ptr(bias) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N,
                                         float(gscale), ctypes.byref(adam) if on else None, _stream(dy)), "nd_bias_grad_adam")
     return g
+
+
+# ---- training of the ViT (include/nested_diffusion.h: nd_gemm_tn_adamw, nd_colsum_adamw, nd_layernorm_wgrad_adamw; the loop: train_transformer.py)
+COLSUM_CHUNK = 64                                          # ND_COLSUM_CHUNK: rows per partial of the column sums
+
+
+def adamw_step(lr: float, t: int, weight_decay: float = 0.1, betas: Tuple[float, float] = (0.9, 0.999),
+               eps: float = 1e-8) -> "_lib.NdAdamwStep":
+    """nd_adamw_step of step t >= 1 (torch.optim.AdamW's `step` after its increment): adam_step's fields plus decay = 1 - lr *
+    weight_decay, all formed in double, as torch's Python does, and rounded to fp32 once."""
+    t = int(t)
+    if t < 1:
+        raise ValueError(f"AdamW steps count from 1 (t={t})")
+    b1, b2 = float(betas[0]), float(betas[1])
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or lr < 0.0 or eps < 0.0 or weight_decay < 0.0:
+        raise ValueError(f"adamw_step needs lr >= 0, eps >= 0, weight_decay >= 0 and betas in [0, 1) (lr={lr}, betas={betas}, eps={eps}, "
+                         f"weight_decay={weight_decay})")
+    return _lib.NdAdamwStep(b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, float(eps),
+                            1.0 - float(lr) * float(weight_decay))
+
+
+def _adamw_state(adamw, return_grad: bool, what: str, dev, numel: int, tensors) -> bool:
+    """Checks of a fused call's in-place tensors ((tensor, name) pairs, `numel` elements each, distinct); True when the call is fused."""
+    if adamw is None:
+        if not return_grad:
+            raise ValueError(f"{what}: adamw=None and return_grad=False: nothing to compute")
+        return False
+    if not isinstance(adamw, _lib.NdAdamwStep):
+        raise TypeError("adamw must be an ops.adamw_step(...) or None")
+    for t, name in tensors:
+        if t is None:
+            raise ValueError(f"{what}: {name} is None in a fused call")
+        _inplace(t, name)
+        if t.numel() != numel or t.device != dev:
+            raise ValueError(f"{name} has {t.numel()} elements on {t.device}; expected {numel} on {dev}")
+    if len({t.data_ptr() for t, _ in tensors}) != len(tensors):
+        raise ValueError(f"{what}: the parameter and moment tensors must be distinct")
+    return True
+
+
+def gemm_tn_adamw(dy: torch.Tensor, x: torch.Tensor, w: Optional[torch.Tensor], m: Optional[torch.Tensor], v: Optional[torch.Tensor], adamw,
+                  gscale: float = 1.0, return_grad: bool = False) -> Optional[torch.Tensor]:
+    """One AdamW step of a row-major fp32 weight w [N, K] on the gradient gscale * (dy^T @ x), dy [M, N], x [M, K], any M >= 1
+    (nd_gemm_tn_adamw: the gradient is formed tile by tile and applied in registers, never written unless asked for).  w, m, v are
+    updated IN PLACE.  adamw: ops.adamw_step(lr, t), or None for the gradient-only call (w, m, v unused).  return_grad: also return the
+    gradient [N, K]."""
+    dy, x = _f32(dy, "dy"), _f32(x, "x")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] < 1 or x.shape[0] != dy.shape[0] or x.device != dy.device:
+        raise ValueError(f"dy is {tuple(dy.shape)} on {dy.device}, x is {tuple(x.shape)} on {x.device}: expected [M >= 1, N >= 1] and [M, K]")
+    (M, N), K = dy.shape, x.shape[1]
+    if K < 16 or K % 16:
+        raise ValueError(f"K must be a positive multiple of 16 (K={K})")
+    on = _adamw_state(adamw, return_grad, "gemm_tn_adamw", dy.device, N * K, ((w, "w"), (m, "m"), (v, "v")))
+    g = torch.empty(N, K, dtype=torch.float32, device=dy.device) if return_grad else None
+    check(_lib.load().nd_gemm_tn_adamw(ptr(dy), ptr(x), ptr(w) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N, K,
+                                       float(gscale), ctypes.byref(adamw) if on else None, _stream(dy)), "nd_gemm_tn_adamw")
+    return g
+
+
+def gemm_tn_plan(N: int, K: int) -> dict:
+    """The tile geometry of nd_gemm_tn_adamw for an [N, K] result (host only)."""
+    out = (ctypes.c_int * 5)()
+    check(_lib.load().nd_gemm_tn_plan(int(N), int(K), out), "nd_gemm_tn_plan")
+    return {"tile_n": out[0], "tile_k": out[1], "m_tile": out[2], "grid_k": out[3], "grid_n": out[4]}
+
+
+def colsum_adamw(dy: torch.Tensor, b: Optional[torch.Tensor], m: Optional[torch.Tensor], v: Optional[torch.Tensor], adamw,
+                 gscale: float = 1.0, return_grad: bool = False) -> Optional[torch.Tensor]:
+    """One AdamW step of a vector parameter b (N elements, any shape) on the gradient gscale * dy.sum(0), dy [M, N], in place
+    (nd_colsum_adamw).  The sum runs over chunks of COLSUM_CHUNK rows, each in row order, the partials in chunk order.  adamw None: the
+    gradient-only call, returns [N]."""
+    dy = _f32(dy, "dy")
+    if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] < 1:
+        raise ValueError(f"dy is {tuple(dy.shape)}: expected [M >= 1, N >= 1]")
+    M, N = dy.shape
+    on = _adamw_state(adamw, return_grad, "colsum_adamw", dy.device, N, ((b, "b"), (m, "m"), (v, "v")))
+    g = torch.empty(N, dtype=torch.float32, device=dy.device) if return_grad else None
+    check(_lib.load().nd_colsum_adamw(ptr(dy), ptr(b) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N,
+                                      float(gscale), ctypes.byref(adamw) if on else None, _stream(dy)), "nd_colsum_adamw")
+    return g
+
+
+def layernorm_wgrad_adamw(x: torch.Tensor, g: torch.Tensor, eps: float, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor],
+                          m_gamma: Optional[torch.Tensor], v_gamma: Optional[torch.Tensor], m_beta: Optional[torch.Tensor],
+                          v_beta: Optional[torch.Tensor], adamw, gscale: float = 1.0, return_grad: bool = False):
+    """One AdamW step of LayerNorm's gamma and beta [dim] on gscale * (sum_r g * xhat, sum_r g), x the LayerNorm's input [rows, dim], g =
+    dL/d(its output), in place (nd_layernorm_wgrad_adamw; xhat recomputed from x as nd_layernorm does).  adamw None: the gradient-only
+    call, returns (dgamma, dbeta)."""
+    x, g = _f32(x, "x"), _f32(g, "g")
+    if x.dim() != 2 or g.shape != x.shape or g.device != x.device or x.shape[0] < 1:
+        raise ValueError(f"x is {tuple(x.shape)}, g is {tuple(g.shape)}: expected two [rows >= 1, dim] tensors on one device")
+    rows, dim = x.shape
+    if dim < 4 or dim % 4 or dim > 2048:
+        raise ValueError(f"dim must be a multiple of 4 in [4, 2048] (dim={dim})")
+    on = _adamw_state(adamw, return_grad, "layernorm_wgrad_adamw", x.device, dim,
+                      ((gamma, "gamma"), (beta, "beta"), (m_gamma, "m_gamma"), (v_gamma, "v_gamma"), (m_beta, "m_beta"), (v_beta, "v_beta")))
+    dg = torch.empty(dim, dtype=torch.float32, device=x.device) if return_grad else None
+    db = torch.empty(dim, dtype=torch.float32, device=x.device) if return_grad else None
+    p = [ptr(t) if on else None for t in (gamma, beta, m_gamma, v_gamma, m_beta, v_beta)]
+    lib = _lib.load()
+    ws = _workspace(lib.nd_layernorm_wgrad_workspace_bytes(rows, dim), x.device)      # the per-chunk partials
+    check(lib.nd_layernorm_wgrad_adamw(ptr(x), ptr(g), *p, ptr(dg), ptr(db), rows, dim, float(eps), float(gscale),
+                                       ctypes.byref(adamw) if on else None, ptr(ws), ws.numel(), _stream(x)), "nd_layernorm_wgrad_adamw")
+    return (dg, db) if return_grad else None
