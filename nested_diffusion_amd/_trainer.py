@@ -1,0 +1,90 @@
+"""What the trainers share (train_mapping.MappingTrainer, train_transformer.ViTTrainer): StepLR, one pass over a loader for training and
+for validation, the reference's epoch loop, and the CLIs' settings."""
+from __future__ import annotations
+
+import os
+import random
+from typing import Optional, Tuple
+
+import torch
+
+from . import ops
+
+
+def step_lr(lr: float, epoch: int, step_size: int, gamma: float) -> float:
+    """StepLR's closed form: the rate during `epoch` (0-based) after `epoch` scheduler steps."""
+    return lr * gamma ** (epoch // step_size)
+
+
+def resolve_settings(args, defaults: dict, max_batch: Optional[int] = None) -> dict:
+    """The run's hyper-parameters: the per-dataset defaults with --epochs / --batch_size / --seed applied."""
+    s = dict(defaults[args.dataset])
+    if args.epochs is not None:
+        s["epochs"] = args.epochs
+    if args.batch_size is not None:
+        s["batch_size"] = args.batch_size
+    if s["batch_size"] < 1 or (max_batch is not None and s["batch_size"] > max_batch):
+        need = "at least 1" if max_batch is None else f"in [1, {max_batch}]"
+        raise SystemExit(f"--batch_size must be {need} (got {s['batch_size']})")
+    s["seed"] = random.randint(0, 10000) if args.seed is None else args.seed
+    return s
+
+
+class EpochTrainer:
+    """The loop around a trainer's step.  A subclass sets device, base_lr, step_size, gamma and epoch (scheduler steps taken) and supplies
+    step(images, labels) -> (loss_sum, n_correct) as device scalars, logits(images), _labels(labels, B) and state_dict()."""
+
+    @property
+    def lr(self) -> float:
+        return step_lr(self.base_lr, self.epoch, self.step_size, self.gamma)
+
+    def scheduler_step(self) -> None:
+        self.epoch += 1
+
+    def evaluate(self, loader) -> Tuple[float, float]:
+        """(mean loss, accuracy) over a loader, forward only; one read-back at the end."""
+        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
+        correct = torch.zeros((), dtype=torch.int64, device=self.device)
+        n = 0
+        for images, labels in loader:
+            logits = self.logits(images)
+            labels = self._labels(labels, logits.shape[0])
+            _, loss, _ = ops.ensemble_xent_grad(logits[None], labels, check_labels=False)
+            loss_sum += loss.sum()
+            correct += (logits.argmax(dim=1) == labels).sum()
+            n += logits.shape[0]
+        if n == 0:
+            raise ValueError("evaluate: the loader is empty")
+        return float(loss_sum) / n, int(correct) / n
+
+    def train_epoch(self, loader) -> Tuple[float, float]:
+        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
+        correct = torch.zeros((), dtype=torch.int64, device=self.device)
+        n = 0
+        for images, labels in loader:
+            l, c = self.step(images, labels)
+            loss_sum += l
+            correct += c
+            n += images.shape[0]
+        if n == 0:
+            raise ValueError("train_epoch: the loader is empty")
+        return float(loss_sum) / n, int(correct) / n
+
+    def _fit(self, train_loader, valid_loader, epochs: int, path: str, title: str) -> dict:
+        """mapping/train_mapping.py:92-165, mapping/train_transformer.py:104-172: train epoch, validate, print the two lines, save to
+        `path` on a strictly better validation accuracy, then the scheduler step; at the end the line '<title> best train Acc ...'.
+        Returns {'best_acc', 'best_train_acc', 'saved_epochs', 'path'}."""
+        best_acc, best_train_acc, saved = 0.0, 0.0, []
+        for epoch in range(int(epochs)):
+            tr_loss, tr_acc = self.train_epoch(train_loader)
+            print(f"Epoch {epoch} Train Loss: {tr_loss:.4f} Acc: {tr_acc:.4f}")
+            va_loss, va_acc = self.evaluate(valid_loader)
+            print(f"Epoch {epoch} Test Loss: {va_loss:.4f} Acc: {va_acc:.4f}")
+            if va_acc > best_acc:
+                best_acc, best_train_acc = va_acc, tr_acc
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                torch.save(self.state_dict(), path)
+                saved.append(epoch)
+            self.scheduler_step()
+        print(f"{title} best train Acc: {best_train_acc:.4f} val Acc: {best_acc:.4f}")
+        return {"best_acc": best_acc, "best_train_acc": best_train_acc, "saved_epochs": saved, "path": path}

@@ -18,7 +18,7 @@ SOURCES = ["nd_skinny_m0.hip", "nd_skinny_m1.hip", "nd_skinny_m2.hip", "nd_sampl
 # per-file flags: the large-M tile kernel keeps its accumulators in VGPRs (see nd_cond_gemm.hpp)
 EXTRA_FLAGS = {"nd_cond_gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "nd_gemm_f32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_gemm_b9.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
-HEADERS = [os.path.join(CSRC, "nd_common.hpp"), os.path.join(CSRC, "nd_cond_gemm.hpp"), os.path.join(CSRC, "nd_rng.hpp"), os.path.join(CSRC, "nd_b9.hpp"), os.path.join(CSRC, "nd_step.hpp"), os.path.join(CSRC, "nd_persist.hpp"), os.path.join(os.path.dirname(HERE), "include", "nested_diffusion.h")]
+HEADERS = [os.path.join(CSRC, "nd_common.hpp"), os.path.join(CSRC, "nd_cond_gemm.hpp"), os.path.join(CSRC, "nd_rng.hpp"), os.path.join(CSRC, "nd_b9.hpp"), os.path.join(CSRC, "nd_step.hpp"), os.path.join(CSRC, "nd_persist.hpp"), os.path.join(CSRC, "nd_host.hpp"), os.path.join(CSRC, "nd_optim.hpp"), os.path.join(os.path.dirname(HERE), "include", "nested_diffusion.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Werror=inline-asm"]
 
 

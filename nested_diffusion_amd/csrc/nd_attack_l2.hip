@@ -17,18 +17,10 @@
 // partial; the finishing pass folds the <= 256 partials of an image with the same tree.  The shape depends on per_image alone, so a sum
 // has the same bits on every run, at every batch size and in every workgroup that finishes it.
 #include "nd_common.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 
 // every operation below is one rounded fp32 op in the listed order: a float32 restatement on the host reproduces the elementwise results
 #pragma clang fp contract(off)
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 namespace {
 

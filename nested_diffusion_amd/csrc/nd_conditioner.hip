@@ -13,9 +13,8 @@
 #include <vector>
 #include <cstring>
 #include <cstdlib>
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 
-int nd_set_err(int code, const char* fmt, ...);
 // nd_ops.hip: Classifier.forward on packed activations (one input pack, hidden layers written in streaming order)
 int nd_mlp_chain(const float* x, const void* const* wpk, const float* const* bias, const int* dims, float* const* hid, float* logits,
                  int M, int dtype, void* ws, size_t ws_bytes, void* stream);

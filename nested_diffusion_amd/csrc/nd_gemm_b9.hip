@@ -16,15 +16,7 @@
 // for the GEMM that consumes it (fc1 -> fc2), so that no separate pass ever splits an activation.
 #include "nd_b9.hpp"
 #include <cstdlib>
-#include "../../include/nested_diffusion.h"
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "nd_host.hpp"
 
 #ifndef B9_DIRECT_STORE
 #define B9_DIRECT_STORE 0          // 1 (variant builds): fp32 outputs stored straight from the accumulators (rounds 4 - early 5)

@@ -1,16 +1,7 @@
 // nd_image.hip -- input-side perturbations of the robustness protocol (diffusion/utils.py:272-414, applied at
 // classification_train_separately.py:726-737).  Elementwise / resampling kernels on [B, C, H, W] fp32 images.
 // gfx950 only.
-#include <hip/hip_runtime.h>
-#include "../../include/nested_diffusion.h"
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "nd_host.hpp"
 
 static inline dim3 grid1(size_t n, int per = 256) {
     const size_t b = (n + per - 1) / per;

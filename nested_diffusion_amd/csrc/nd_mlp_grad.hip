@@ -18,15 +18,7 @@
 // Rows n >= N of the image are the zero padding of nd_pack_rows; their dy operand is zero-filled in registers, never read (0 * garbage
 // would be NaN), and so are the rows m >= M of the last 16-row tile.
 #include "nd_common.hpp"
-#include "../../include/nested_diffusion.h"
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "nd_host.hpp"
 
 namespace {
 

@@ -20,19 +20,12 @@
 // gradient of a padding row is forced to 0 after the MFMA and its lanes skip the update, so neither a NaN in x nor eps = 0 reaches the
 // padding: it stays exactly 0.
 #include "nd_common.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
+#include "nd_optim.hpp"
 
-// every operation of the update is one rounded fp32 op in the listed order (division and square root correctly rounded, denormals kept):
-// a float32 restatement on the host reproduces it bit for bit on every input, the edges of fp32 included (tests/test_gpu_mlp_edges.py)
+// every operation of the update (nd_optim.hpp) and of the sums is one rounded fp32 op in the listed order: a float32 restatement on the
+// host reproduces it bit for bit on every input, the edges of fp32 included (tests/test_gpu_mlp_edges.py)
 #pragma clang fp contract(off)
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 namespace {
 
@@ -48,14 +41,6 @@ WgPlan wg_plan(int N, int K) {
     if (want > nrb) want = nrb;
     const int rbs = (nrb + want - 1) / want;
     return WgPlan{gx, (nrb + rbs - 1) / rbs, rbs};
-}
-
-// torch 1.10 torch/optim/_functional.py adam (no weight decay, no amsgrad)
-__device__ __forceinline__ void mt_adam(float& w, float& m, float& v, float g, const nd_adam_step& a) {
-    m = (m * a.beta1) + (g * a.one_minus_beta1);
-    v = (v * a.beta2) + ((g * g) * a.one_minus_beta2);
-    const float denom = (sqrtf(v) / a.sqrt_bc2) + a.eps;
-    w = w - a.step_size * (m / denom);
 }
 
 template <int MS, bool ADAM>
@@ -118,10 +103,10 @@ __global__ __launch_bounds__(WG_WAVES * 64) void k_wgrad_adam(const float* __res
             if (i < nb) {
                 if (g_out) *reinterpret_cast<float4*>(g_out + off[i]) = g;
                 if (ADAM && live) {                       // a padding row is not updated at all: it stays 0 whatever eps is (0 / (0 + 0) would be NaN)
-                    mt_adam(w4[i].x, m4[i].x, v4[i].x, g.x, a);
-                    mt_adam(w4[i].y, m4[i].y, v4[i].y, g.y, a);
-                    mt_adam(w4[i].z, m4[i].z, v4[i].z, g.z, a);
-                    mt_adam(w4[i].w, m4[i].w, v4[i].w, g.w, a);
+                    nd_optim_update(w4[i].x, m4[i].x, v4[i].x, g.x, a);
+                    nd_optim_update(w4[i].y, m4[i].y, v4[i].y, g.y, a);
+                    nd_optim_update(w4[i].z, m4[i].z, v4[i].z, g.z, a);
+                    nd_optim_update(w4[i].w, m4[i].w, v4[i].w, g.w, a);
                 }
                 if (ADAM) {                               // (the whole wave stores: the padding lanes write back what they read)
                     *reinterpret_cast<float4*>(w + off[i]) = w4[i];
@@ -152,14 +137,12 @@ __global__ __launch_bounds__(256) void k_bias_grad_adam(const float* __restrict_
     if (g_out) g_out[n] = g;
     if (adam) {
         float wv = b[n], mv = mom[n], vv = var[n];
-        mt_adam(wv, mv, vv, g, a);
+        nd_optim_update(wv, mv, vv, g, a);
         b[n] = wv;
         mom[n] = mv;
         var[n] = vv;
     }
 }
-
-bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
 
 }  // namespace
 
@@ -187,12 +170,13 @@ extern "C" int nd_linear_wgrad_adam(const float* dy, const float* x, void* w_pac
     if (M < 1 || M > ND_LINEAR_BWD_MAX_M) return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam needs 1 <= M <= %d (M=%d)", ND_LINEAR_BWD_MAX_M, M);
     if (K < 16 || K % 16) return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam needs K a positive multiple of 16 (K=%d)", K);
     if (N < 1) return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam needs N >= 1 (N=%d)", N);
-    if (misaligned(dy, 3) || misaligned(x, 3) || misaligned(w_packed, 15) || misaligned(m_packed, 15) || misaligned(v_packed, 15) ||
-        misaligned(g_out_packed, 15))
+    if (nd_misaligned(dy, 3) || nd_misaligned(x, 3) || nd_misaligned(w_packed, 15) || nd_misaligned(m_packed, 15) || nd_misaligned(v_packed, 15) ||
+        nd_misaligned(g_out_packed, 15))
         return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam: misaligned tensor (the images 16 bytes, dy / x 4)");
-    if (a && (w_packed == m_packed || w_packed == v_packed || m_packed == v_packed || g_out_packed == w_packed || g_out_packed == m_packed ||
-              g_out_packed == v_packed))
-        return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam: the images w, m, v and g_out must be distinct buffers");
+    if (a) {
+        const void* p[4] = {w_packed, m_packed, v_packed, g_out_packed};
+        if (nd_any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "linear_wgrad_adam: the images w, m, v and g_out must be distinct buffers");
+    }
     const WgPlan p = wg_plan(N, K);
     const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
     hipStream_t st = (hipStream_t)stream;
@@ -215,10 +199,12 @@ extern "C" int nd_bias_grad_adam(const float* dy, float* b, float* m, float* v, 
     if (a && !v) return nd_set_err(ND_ERR_ARG, "bias_grad_adam: NULL tensor v");
     if (M < 1) return nd_set_err(ND_ERR_ARG, "bias_grad_adam needs M >= 1 (M=%d)", M);
     if (N < 1) return nd_set_err(ND_ERR_ARG, "bias_grad_adam needs N >= 1 (N=%d)", N);
-    if (misaligned(dy, 3) || misaligned(b, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(g_out, 3))
+    if (nd_misaligned(dy, 3) || nd_misaligned(b, 3) || nd_misaligned(m, 3) || nd_misaligned(v, 3) || nd_misaligned(g_out, 3))
         return nd_set_err(ND_ERR_ARG, "bias_grad_adam: misaligned tensor");
-    if (a && (b == m || b == v || m == v || g_out == b || g_out == m || g_out == v))
-        return nd_set_err(ND_ERR_ARG, "bias_grad_adam: b, m, v and g_out must be distinct buffers");
+    if (a) {
+        const void* p[4] = {b, m, v, g_out};
+        if (nd_any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "bias_grad_adam: b, m, v and g_out must be distinct buffers");
+    }
     const nd_adam_step av = a ? *a : nd_adam_step{};
     hipLaunchKernelGGL(k_bias_grad_adam, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, b, m, v, g_out, M, N, gscale, av,
                        a ? 1 : 0);
@@ -231,7 +217,7 @@ extern "C" int nd_unpack_rows(const void* src_packed, float* dst, int R, int K, 
     if (!dst) return nd_set_err(ND_ERR_ARG, "unpack_rows: NULL tensor dst");
     if (dtype != ND_DTYPE_F32) return nd_set_err(ND_ERR_ARG, "unpack_rows: dtype must be ND_DTYPE_F32: only fp32 (frag16) images are unpacked");
     if (R < 1 || K < 16 || K % 16) return nd_set_err(ND_ERR_ARG, "unpack_rows needs R >= 1 and K a positive multiple of 16 (R=%d, K=%d)", R, K);
-    if (misaligned(src_packed, 15) || misaligned(dst, 15)) return nd_set_err(ND_ERR_ARG, "unpack_rows: misaligned tensor (16 bytes)");
+    if (nd_misaligned(src_packed, 15) || nd_misaligned(dst, 15)) return nd_set_err(ND_ERR_ARG, "unpack_rows: misaligned tensor (16 bytes)");
     const size_t n16 = nd_packed_bytes_dt(R, K, 0) / 16, want = (n16 + 255) / 256;
     const dim3 grid((unsigned)(want > 8192 ? 8192 : want));
     hipLaunchKernelGGL(k_unpack_rows, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src_packed, dst, R, K);

@@ -2,15 +2,7 @@
 // gfx950 only.
 #include "nd_common.hpp"
 #include "nd_cond_gemm.hpp"
-#include "../../include/nested_diffusion.h"
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "nd_host.hpp"
 
 // ---- packing ---------------------------------------------------------------------------------
 static int bad_dtype(int dtype) { return dtype != ND_DTYPE_F32 && dtype != ND_DTYPE_F16; }

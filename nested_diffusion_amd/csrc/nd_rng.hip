@@ -11,15 +11,7 @@
 // over ranks or on launch geometry.  The four 32-bit outputs become four standard normals by Box-Muller:
 //   u1 = (x0 + 1) * 2^-32 in (0, 1], u2 = x1 * 2^-32 in [0, 1):  r = sqrt(-2 ln u1), (z0, z1) = r * (cos, sin)(2 pi u2); same for (x2, x3).
 #include "nd_rng.hpp"
-#include "../../include/nested_diffusion.h"
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "nd_host.hpp"
 
 __device__ __forceinline__ void nd_philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll

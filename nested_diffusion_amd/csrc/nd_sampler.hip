@@ -11,7 +11,7 @@
 #include "nd_b9.hpp"
 #include "nd_persist.hpp"
 #include "nd_rng.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 
 #include <map>
 #include <string>
@@ -44,12 +44,6 @@ int nd_set_err(int code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 // eps[m, c] = sum over the n-tiles of lin3's projected partials (lin4.bias added by the caller); fixed
 // reduction tree (thread-strided, wave shuffle, then waves in order) => reproducible.  All C classes

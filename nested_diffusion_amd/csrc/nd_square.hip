@@ -13,20 +13,10 @@
 // Windows start at arbitrary (vh, vw) and W need not be a multiple of 4: every window access is a scalar fp32 load or store, consecutive
 // lanes on consecutive w (coalesced along a window row); nothing assumes 16-byte alignment inside an image.  A window of side s moves
 // Cin * s * s elements per image, against Cin * H * W for the whole-array formulation.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 
 // every operation below is one rounded fp32 op in the listed order: a float32 restatement on the host reproduces every array bit for bit
 #pragma clang fp contract(off)
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 namespace {
 

@@ -3,16 +3,8 @@
 // f32-input MFMA (exact f32 products).
 #include "nd_common.hpp"
 #include "nd_b9.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 #include <cstdlib>
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 // fp32 GEMM kernel: nd_gemm_f32.hip (its own translation unit, accumulators in VGPRs)
 hipError_t nd_launch_gemm_nt_128x64(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int K, int N,

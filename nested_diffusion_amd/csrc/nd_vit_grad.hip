@@ -20,19 +20,11 @@
 //   k_apgd_update       APGD's per-element work of one iteration: best / best-adversarial copies, restore, the momentum step
 #include "nd_common.hpp"
 #include "nd_b9.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
 
 // Every product below is rounded to fp32 before it is used: no contraction into a following add (in particular not into the first
 // subtraction of nd_b9_split, which would make a frag32b3 image differ from the split of the fp32 value stored beside it).
 #pragma clang fp contract(off)
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm backward, one wave per row: dx = rstd * (gg - mean(gg) - xh * mean(gg * xh)) (+ res), gg = g * gamma, xh = (x - mean) * rstd.

@@ -23,19 +23,12 @@
 // shorter); a chunk's partial is p = 0, p += term(r) for r in row order; the result is acc = 0, acc += p in chunk order.  A function of
 // the row count alone: not of the width, the grid or which wave summed a chunk.
 #include "nd_common.hpp"
-#include "../../include/nested_diffusion.h"
+#include "nd_host.hpp"
+#include "nd_optim.hpp"
 
-// every operation of the update and of the sums is one rounded fp32 op in the listed order (division and square root correctly
-// rounded): a float32 restatement on the host reproduces them bit for bit (tests/test_gpu_vit_train.py)
+// every operation of the update (nd_optim.hpp) and of the sums is one rounded fp32 op in the listed order: a float32 restatement on the
+// host reproduces them bit for bit (tests/test_gpu_vit_train.py)
 #pragma clang fp contract(off)
-
-int nd_set_err(int code, const char* fmt, ...);
-#define HIP_CHECK(expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
 
 namespace {
 
@@ -45,15 +38,6 @@ constexpr int GT_LD = 80;               // LDS row stride in floats
 constexpr int GT_PER = GT_MT * 64 / 256;   // elements of each operand a thread stages
 
 constexpr int CS_CHUNK = ND_COLSUM_CHUNK;
-
-// torch 1.10 torch/optim/_functional.py adamw (no amsgrad)
-__device__ __forceinline__ void vt_adamw(float& w, float& m, float& v, float g, const nd_adamw_step& a) {
-    w = w * a.decay;
-    m = (m * a.beta1) + (g * a.one_minus_beta1);
-    v = (v * a.beta2) + ((g * g) * a.one_minus_beta2);
-    const float denom = (sqrtf(v) / a.sqrt_bc2) + a.eps;
-    w = w - a.step_size * (m / denom);
-}
 
 template <bool ADAM>
 __global__ __launch_bounds__(256) void k_gemm_tn_adamw(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ w,
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn_adamw(const float* __restrict__
                     if (g_out) g_out[off] = g;
                     if (ADAM) {
                         float wv = w[off], mv = mom[off], vv = var[off];
-                        vt_adamw(wv, mv, vv, g, a);
+                        nd_optim_update(wv, mv, vv, g, a);
                         w[off] = wv;
                         mom[off] = mv;
                         var[off] = vv;
@@ -168,7 +152,7 @@ __global__ __launch_bounds__(COLS * GROUPS) void k_colsum_adamw(const float* __r
     if (g_out) g_out[n] = g;
     if (adam) {
         float wv = b[n], mv = mom[n], vv = var[n];
-        vt_adamw(wv, mv, vv, g, a);
+        nd_optim_update(wv, mv, vv, g, a);
         b[n] = wv;
         mom[n] = mv;
         var[n] = vv;
@@ -252,12 +236,12 @@ __global__ __launch_bounds__(64) void k_ln_wgrad_finish(const float* __restrict_
     if (go_beta) go_beta[c] = db;
     if (adam) {
         float wv = gamma[c], mv = m_gamma[c], vv = v_gamma[c];
-        vt_adamw(wv, mv, vv, dg, a);
+        nd_optim_update(wv, mv, vv, dg, a);
         gamma[c] = wv;
         m_gamma[c] = mv;
         v_gamma[c] = vv;
         wv = beta[c], mv = m_beta[c], vv = v_beta[c];
-        vt_adamw(wv, mv, vv, db, a);
+        nd_optim_update(wv, mv, vv, db, a);
         beta[c] = wv;
         m_beta[c] = mv;
         v_beta[c] = vv;
@@ -265,16 +249,6 @@ __global__ __launch_bounds__(64) void k_ln_wgrad_finish(const float* __restrict_
 }
 
 bool ln_shape_ok(int rows, int dim) { return rows >= 1 && dim >= 4 && dim % 4 == 0 && dim <= 2048; }
-
-bool misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
-
-// true when two of the non-NULL pointers are the same buffer
-bool any_equal(const void* const* p, int n) {
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (p[i] && p[i] == p[j]) return true;
-    return false;
-}
 
 }  // namespace
 
@@ -301,11 +275,11 @@ extern "C" int nd_gemm_tn_adamw(const float* dy, const float* x, float* w, float
     if (N < 1) return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw needs N >= 1 (N=%d)", N);
     if (K < 16 || K % 16) return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw needs K a positive multiple of 16 (K=%d)", K);
     if ((N + GT_TN - 1) / GT_TN > 65535) return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw: N too large (N=%d)", N);
-    if (misaligned(dy, 3) || misaligned(x, 3) || misaligned(w, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(g_out, 3))
+    if (nd_misaligned(dy, 3) || nd_misaligned(x, 3) || nd_misaligned(w, 3) || nd_misaligned(m, 3) || nd_misaligned(v, 3) || nd_misaligned(g_out, 3))
         return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw: misaligned tensor");
     if (a) {
         const void* p[4] = {w, m, v, g_out};
-        if (any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw: w, m, v and g_out must be distinct buffers");
+        if (nd_any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "gemm_tn_adamw: w, m, v and g_out must be distinct buffers");
     }
     const dim3 grid((unsigned)((K + GT_TK - 1) / GT_TK), (unsigned)((N + GT_TN - 1) / GT_TN));
     const nd_adamw_step av = a ? *a : nd_adamw_step{};
@@ -325,11 +299,11 @@ extern "C" int nd_colsum_adamw(const float* dy, float* b, float* m, float* v, fl
     if (a && !v) return nd_set_err(ND_ERR_ARG, "colsum_adamw: NULL tensor v");
     if (M < 1) return nd_set_err(ND_ERR_ARG, "colsum_adamw needs M >= 1 (M=%d)", M);
     if (N < 1) return nd_set_err(ND_ERR_ARG, "colsum_adamw needs N >= 1 (N=%d)", N);
-    if (misaligned(dy, 3) || misaligned(b, 3) || misaligned(m, 3) || misaligned(v, 3) || misaligned(g_out, 3))
+    if (nd_misaligned(dy, 3) || nd_misaligned(b, 3) || nd_misaligned(m, 3) || nd_misaligned(v, 3) || nd_misaligned(g_out, 3))
         return nd_set_err(ND_ERR_ARG, "colsum_adamw: misaligned tensor");
     if (a) {
         const void* p[4] = {b, m, v, g_out};
-        if (any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "colsum_adamw: b, m, v and g_out must be distinct buffers");
+        if (nd_any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "colsum_adamw: b, m, v and g_out must be distinct buffers");
     }
     const nd_adamw_step av = a ? *a : nd_adamw_step{};
     if (M > 2 * CS_CHUNK)
@@ -360,12 +334,12 @@ extern "C" int nd_layernorm_wgrad_adamw(const float* x, const float* g, float* g
     const size_t need = nd_layernorm_wgrad_workspace_bytes(rows, dim);
     if (!ws || ws_bytes < need)
         return nd_set_err(ND_ERR_ARG, "layernorm_wgrad_adamw: workspace of %zu bytes, %zu needed (nd_layernorm_wgrad_workspace_bytes)", ws ? ws_bytes : (size_t)0, need);
-    if (misaligned(x, 15) || misaligned(g, 15) || misaligned(ws, 15) || misaligned(gamma, 3) || misaligned(beta, 3) || misaligned(m_gamma, 3) ||
-        misaligned(v_gamma, 3) || misaligned(m_beta, 3) || misaligned(v_beta, 3) || misaligned(g_out_gamma, 3) || misaligned(g_out_beta, 3))
+    if (nd_misaligned(x, 15) || nd_misaligned(g, 15) || nd_misaligned(ws, 15) || nd_misaligned(gamma, 3) || nd_misaligned(beta, 3) || nd_misaligned(m_gamma, 3) ||
+        nd_misaligned(v_gamma, 3) || nd_misaligned(m_beta, 3) || nd_misaligned(v_beta, 3) || nd_misaligned(g_out_gamma, 3) || nd_misaligned(g_out_beta, 3))
         return nd_set_err(ND_ERR_ARG, "layernorm_wgrad_adamw: misaligned tensor (x / g / workspace 16 bytes, the rest 4)");
     if (a) {
         const void* p[8] = {gamma, beta, m_gamma, v_gamma, m_beta, v_beta, g_out_gamma, g_out_beta};
-        if (any_equal(p, 8)) return nd_set_err(ND_ERR_ARG, "layernorm_wgrad_adamw: the parameter, moment and g_out tensors must be distinct buffers");
+        if (nd_any_equal(p, 8)) return nd_set_err(ND_ERR_ARG, "layernorm_wgrad_adamw: the parameter, moment and g_out tensors must be distinct buffers");
     }
     const nd_adamw_step av = a ? *a : nd_adamw_step{};
     hipStream_t st = (hipStream_t)stream;

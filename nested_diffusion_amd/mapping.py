@@ -174,17 +174,23 @@ class VisionTransformer:
             self._wT = wT
         return self._wT
 
-    def _block_grad(self, i: int, r: dict, dy: torch.Tensor, dy_img: "ops.SplitMatrix", B: int):
-        """dL/d(block input) from dy = dL/d(block output): fp32 and its frag32b3 image."""
+    def _block_grad(self, i: int, r: dict, dy: torch.Tensor, dy_img: "ops.SplitMatrix", B: int, keep: Optional[dict] = None):
+        """dL/d(block input) from dy = dL/d(block output): fp32 and its frag32b3 image.  keep (training): a dict that receives the fp32
+        gradients the weight gradients read -- du (fc1's output), dh2 (norm2's), dx2 (attn.proj's), dqkv (attn.qkv's), dh1 (norm1's); the
+        GELU and attention gradients then write fp32 beside their images.  None (the attacks): images only there, the same launches."""
         wT, p, pre = self._wT, self.p, f"blocks.{i}."
         N = dy.shape[0] // B
+        kept = keep is not None
         dg = ops.gemm_split(dy_img, wT[pre + "mlp.fc2.weight"])
-        dh = ops.gemm_split(ops.gelu_grad_split(r["u"], dg), wT[pre + "mlp.fc1.weight"])
-        dx2, dx2_img = ops.layernorm_grad(r["x2"], p[pre + "norm2.weight"], dh, LN_EPS, residual=dy, want_split=True)
+        du = ops.gelu_grad_split(r["u"], dg, want_out=kept)                     # the image, or (fp32, image)
+        dh2 = ops.gemm_split(du[1] if kept else du, wT[pre + "mlp.fc1.weight"])
+        dx2, dx2_img = ops.layernorm_grad(r["x2"], p[pre + "norm2.weight"], dh2, LN_EPS, residual=dy, want_split=True)
         da = ops.gemm_split(dx2_img, wT[pre + "attn.proj.weight"])
-        dqkv = ops.attention_grad(r["qkv"], r["o"], da, B, N, self.num_heads, want_out=False, want_split=True)
-        dh = ops.gemm_split(dqkv, wT[pre + "attn.qkv.weight"])
-        return ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh, LN_EPS, residual=dx2, want_split=True)
+        dqkv = ops.attention_grad(r["qkv"], r["o"], da, B, N, self.num_heads, want_out=kept, want_split=True)
+        dh1 = ops.gemm_split(dqkv[1] if kept else dqkv, wT[pre + "attn.qkv.weight"])
+        if kept:
+            keep.update(du=du[0], dh2=dh2, dx2=dx2, dqkv=dqkv[0], dh1=dh1)
+        return ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh1, LN_EPS, residual=dx2, want_split=True)
 
     def _forward_recorded(self, x: torch.Tensor):
         """The forward of forward(), same kernels in the same order, keeping what the input gradient needs:
@@ -207,19 +213,33 @@ class VisionTransformer:
         logits = ops.linear(cls, self.p["head.weight"], self.p["head.bias"])
         return logits, cls_in, recs, B, N, H, W
 
-    def _input_backward(self, dcls: torch.Tensor, cls_in: torch.Tensor, recs: list, B: int, N: int, H: int, W: int) -> torch.Tensor:
-        """dL/dx from dcls = dL/d(the final norm's output on the cls token): the backward chain every head gradient shares."""
-        wT = self._wT
-        dcls = ops.layernorm_grad(cls_in, self.p["norm.weight"], dcls, LN_EPS)
+    def _token_backward(self, dcls: torch.Tensor, cls_in: torch.Tensor, recs: list, B: int, N: int, per_block=None) -> torch.Tensor:
+        """dL/d(the tokens entering block 0) [B*N, embed] from dcls = dL/d(the final norm's output on the cls token): the backward chain
+        every head gradient and the trainer share.  recs[i] is released once block i is behind.  per_block (training): called as
+        per_block(i, rec, dy, kept) right after the chain launches of each stage, top down, with dy = dL/d(that stage's output) -- first
+        for the final norm (i = depth, rec and kept None, dy = dcls), then for every block (rec = recs[i], kept = _block_grad's keep); the
+        trainer issues its weight-gradient launches from it.  None: no fp32 gradient is kept."""
+        dcls_in = ops.layernorm_grad(cls_in, self.p["norm.weight"], dcls, LN_EPS)
+        if per_block is not None:
+            per_block(self.depth, None, dcls, None)
         dy = torch.zeros(B, N, self.embed_dim, dtype=torch.float32, device=dcls.device)
-        dy[:, 0] = dcls                                       # only the cls token reaches the head
+        dy[:, 0] = dcls_in                                    # only the cls token reaches the head
         dy = dy.reshape(B * N, self.embed_dim)
         dy_img = ops.split_rows(dy)
         for i in reversed(range(self.depth)):
-            dy, dy_img = self._block_grad(i, recs[i], dy, dy_img, B)
+            kept = {} if per_block is not None else None
+            dx, dx_img = self._block_grad(i, recs[i], dy, dy_img, B, kept)
+            if per_block is not None:
+                per_block(i, recs[i], dy, kept)
+            dy, dy_img = dx, dx_img
             recs[i] = None
+        return dy
+
+    def _input_backward(self, dcls: torch.Tensor, cls_in: torch.Tensor, recs: list, B: int, N: int, H: int, W: int) -> torch.Tensor:
+        """dL/dx from dcls: _token_backward, then the patch embedding's input gradient."""
+        dy = self._token_backward(dcls, cls_in, recs, B, N)
         dpatch = dy.reshape(B, N, self.embed_dim)[:, 1:].reshape(-1, self.embed_dim).contiguous()   # cls token / pos_embed: no input path
-        dcols = ops.gemm_split(dpatch, wT["patch_embed"])
+        dcols = ops.gemm_split(dpatch, self._wT["patch_embed"])
         return ops.unpatchify(dcols, B, self.in_chans, H, W, self.patch)
 
     def input_grad(self, x: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

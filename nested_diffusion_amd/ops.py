@@ -410,9 +410,11 @@ def attention_grad(qkv: torch.Tensor, o: torch.Tensor, dout: torch.Tensor, B: in
     return _image_or_tensor(out, osp, want_out, want_split)
 
 
-def xent_head_grad(logits: torch.Tensor, labels: torch.Tensor, head_w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+def xent_head_grad(logits: torch.Tensor, labels: torch.Tensor, head_w: torch.Tensor,
+                   check_labels: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
     """(dfeat [B, E] = (softmax(logits) - onehot(labels)) . head_w, per-image cross-entropy [B]): the gradient of
-    crossentropy(logits, labels).sum() with respect to the head's input."""
+    crossentropy(logits, labels).sum() with respect to the head's input.  check_labels=False skips the label-range check, the call's only
+    read-back."""
     logits, head_w = _f32(logits, "logits"), _f32(head_w, "head_w")
     B, C = logits.shape
     if head_w.dim() != 2 or head_w.shape[0] != C:
@@ -420,7 +422,7 @@ def xent_head_grad(logits: torch.Tensor, labels: torch.Tensor, head_w: torch.Ten
     labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
     if labels.shape != (B,):
         raise ValueError(f"labels must be [{B}]")
-    if B and (int(labels.min()) < 0 or int(labels.max()) >= C):
+    if check_labels and B and (int(labels.min()) < 0 or int(labels.max()) >= C):
         raise ValueError(f"labels must lie in [0, {C})")
     E = head_w.shape[1]
     dfeat = torch.empty(B, E, dtype=torch.float32, device=logits.device)
@@ -909,33 +911,67 @@ def ensemble_xent_grad(logits: torch.Tensor, labels: Optional[torch.Tensor] = No
     return P, loss, dlogits
 
 
-def adam_step(lr: float, t: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8) -> "_lib.NdAdamStep":
-    """nd_adam_step of step t >= 1 (torch.optim.Adam's `step` after its increment): the bias corrections are formed in double, as torch's
-    Python does, and every field is rounded to fp32 once: step_size = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t)."""
+def _adam_fields(what: str, lr: float, t: int, betas: Tuple[float, float], eps: float) -> tuple:
+    """The seven fields nd_adam_step and nd_adamw_step share, formed in double, as torch's Python does (ctypes rounds each to fp32 once):
+    step_size = lr / (1 - beta1^t), sqrt_bc2 = sqrt(1 - beta2^t)."""
     t = int(t)
     if t < 1:
-        raise ValueError(f"Adam steps count from 1 (t={t})")
+        raise ValueError(f"{what}: steps count from 1 (t={t})")
     b1, b2 = float(betas[0]), float(betas[1])
     if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or lr < 0.0 or eps < 0.0:
-        raise ValueError(f"adam_step needs lr >= 0, eps >= 0 and betas in [0, 1) (lr={lr}, betas={betas}, eps={eps})")
-    return _lib.NdAdamStep(b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, float(eps))
+        raise ValueError(f"{what} needs lr >= 0, eps >= 0 and betas in [0, 1) (lr={lr}, betas={betas}, eps={eps})")
+    return b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, float(eps)
 
 
-def _adam_images(weight: PackedWeight, m, v, adam, return_grad: bool, what: str):
-    if adam is None:
+def adam_step(lr: float, t: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8) -> "_lib.NdAdamStep":
+    """nd_adam_step of step t >= 1 (torch.optim.Adam's `step` after its increment)."""
+    return _lib.NdAdamStep(*_adam_fields("adam_step", lr, t, betas, eps))
+
+
+def adamw_step(lr: float, t: int, weight_decay: float = 0.1, betas: Tuple[float, float] = (0.9, 0.999),
+               eps: float = 1e-8) -> "_lib.NdAdamwStep":
+    """nd_adamw_step of step t >= 1 (torch.optim.AdamW's `step` after its increment): adam_step's fields plus decay = 1 - lr *
+    weight_decay, formed in double like them."""
+    if weight_decay < 0.0:
+        raise ValueError(f"adamw_step needs weight_decay >= 0 (weight_decay={weight_decay})")
+    return _lib.NdAdamwStep(*_adam_fields("adamw_step", lr, t, betas, eps), 1.0 - float(lr) * float(weight_decay))
+
+
+_STEP_ARG = {_lib.NdAdamStep: "adam", _lib.NdAdamwStep: "adamw"}
+
+
+def _fused_state(step, step_type, return_grad: bool, what: str, dev, state) -> bool:
+    """The checks every gradient + optimizer call shares; True when the call is fused.  step: the call's ops.adam_step / ops.adamw_step
+    (a step_type), or None for the gradient-only call, which then needs return_grad.  state: (tensor-or-image, name, size) of every
+    buffer the update writes in place, all distinct: a float32 contiguous tensor on `dev` of shape `size` (a tuple) or of `size` elements
+    (an int), or -- `size` a PackedWeight -- a PackedWeight image of its (N, K, dtype, device)."""
+    arg = _STEP_ARG[step_type]
+    if step is None:
         if not return_grad:
-            raise ValueError(f"{what}: adam=None and return_grad=False: nothing to compute")
-        return
-    if not isinstance(adam, _lib.NdAdamStep):
-        raise TypeError("adam must be an ops.adam_step(...) or None")
-    for img, name in ((m, "m"), (v, "v")):
-        if not isinstance(img, PackedWeight):
-            raise TypeError(f"{name} must be a PackedWeight (weight.zeros_like())")
-        if (img.N, img.K, img.dtype) != (weight.N, weight.K, weight.dtype) or img.data.device != weight.data.device:
-            raise ValueError(f"{name} is a [{img.N}, {img.K}] image on {img.data.device}; expected weight's [{weight.N}, {weight.K}] on "
-                             f"{weight.data.device}")
-    if len({weight.data.data_ptr(), m.data.data_ptr(), v.data.data_ptr()}) != 3:
-        raise ValueError("weight, m and v must be distinct images")
+            raise ValueError(f"{what}: {arg}=None and return_grad=False: nothing to compute")
+        return False
+    if not isinstance(step, step_type):
+        raise TypeError(f"{arg} must be an ops.{arg}_step(...) or None")
+    ptrs = set()
+    for t, name, size in state:
+        if isinstance(size, PackedWeight):
+            if not isinstance(t, PackedWeight):
+                raise TypeError(f"{name} must be a PackedWeight (weight.zeros_like())")
+            if (t.N, t.K, t.dtype) != (size.N, size.K, size.dtype) or t.data.device != size.data.device:
+                raise ValueError(f"{name} is a [{t.N}, {t.K}] image on {t.data.device}; expected weight's [{size.N}, {size.K}] on "
+                                 f"{size.data.device}")
+            t = t.data
+        else:
+            if t is None:
+                raise ValueError(f"{what}: {name} is None in a fused call")
+            shaped = isinstance(size, tuple)
+            _inplace(t, name, shape=size if shaped else None)
+            if (not shaped and t.numel() != size) or t.device != dev:
+                raise ValueError(f"{name} has {t.numel()} elements on {t.device}; expected {size} on {dev}")
+        ptrs.add(t.data_ptr())
+    if len(ptrs) != len(state):
+        raise ValueError(f"{what}: the parameter and moment buffers must be distinct")
+    return True
 
 
 def linear_wgrad_adam(dy: torch.Tensor, x: torch.Tensor, weight: PackedWeight, m: Optional[PackedWeight], v: Optional[PackedWeight], adam,
@@ -963,11 +999,11 @@ def linear_wgrad_adam(dy: torch.Tensor, x: torch.Tensor, weight: PackedWeight, m
         raise ValueError(f"x is {tuple(x.shape)} on {x.device}; expected [{M}, {K}] on {dy.device}")
     if weight.data.device != dy.device:
         raise ValueError(f"weight is on {weight.data.device}, dy on {dy.device}")
-    _adam_images(weight, m, v, adam, return_grad, "linear_wgrad_adam")
+    on = _fused_state(adam, _lib.NdAdamStep, return_grad, "linear_wgrad_adam", dy.device, ((weight, "weight", weight), (m, "m", weight), (v, "v", weight)))
     g = weight.zeros_like() if return_grad else None
-    check(lib.nd_linear_wgrad_adam(ptr(dy), ptr(x), ptr(weight.data), ptr(m.data) if adam is not None else None,
-                                   ptr(v.data) if adam is not None else None, ptr(g.data) if g is not None else None, M, N, K, weight.dtype,
-                                   float(gscale), ctypes.byref(adam) if adam is not None else None, _stream(dy)), "nd_linear_wgrad_adam")
+    check(lib.nd_linear_wgrad_adam(ptr(dy), ptr(x), ptr(weight.data), ptr(m.data) if on else None, ptr(v.data) if on else None,
+                                   ptr(g.data) if g is not None else None, M, N, K, weight.dtype, float(gscale),
+                                   ctypes.byref(adam) if on else None, _stream(dy)), "nd_linear_wgrad_adam")
     return g
 
 
@@ -987,20 +1023,8 @@ def bias_grad_adam(dy: torch.Tensor, bias: torch.Tensor, m: Optional[torch.Tenso
     if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] < 1:
         raise ValueError(f"dy is {tuple(dy.shape)}: expected [M >= 1, N >= 1]")
     M, N = dy.shape
-    if adam is None:
-        if not return_grad:
-            raise ValueError("bias_grad_adam: adam=None and return_grad=False: nothing to compute")
-    else:
-        if not isinstance(adam, _lib.NdAdamStep):
-            raise TypeError("adam must be an ops.adam_step(...) or None")
-        for t, name in ((bias, "bias"), (m, "m"), (v, "v")):
-            _inplace(t, name, shape=(N,))
-            if t.device != dy.device:
-                raise ValueError(f"{name} is on {t.device}, dy on {dy.device}")
-        if len({bias.data_ptr(), m.data_ptr(), v.data_ptr()}) != 3:
-            raise ValueError("bias, m and v must be distinct tensors")
+    on = _fused_state(adam, _lib.NdAdamStep, return_grad, "bias_grad_adam", dy.device, ((bias, "bias", (N,)), (m, "m", (N,)), (v, "v", (N,))))
     g = torch.empty(N, dtype=torch.float32, device=dy.device) if return_grad else None
-    on = adam is not None
     check(_lib.load().nd_bias_grad_adam(ptr(dy), ptr(bias) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N,
                                         float(gscale), ctypes.byref(adam) if on else None, _stream(dy)), "nd_bias_grad_adam")
     return g
@@ -1008,40 +1032,6 @@ def bias_grad_adam(dy: torch.Tensor, bias: torch.Tensor, m: Optional[torch.Tenso
 
 # ---- training of the ViT (include/nested_diffusion.h: nd_gemm_tn_adamw, nd_colsum_adamw, nd_layernorm_wgrad_adamw; the loop: train_transformer.py)
 COLSUM_CHUNK = 64                                          # ND_COLSUM_CHUNK: rows per partial of the column sums
-
-
-def adamw_step(lr: float, t: int, weight_decay: float = 0.1, betas: Tuple[float, float] = (0.9, 0.999),
-               eps: float = 1e-8) -> "_lib.NdAdamwStep":
-    """nd_adamw_step of step t >= 1 (torch.optim.AdamW's `step` after its increment): adam_step's fields plus decay = 1 - lr *
-    weight_decay, all formed in double, as torch's Python does, and rounded to fp32 once."""
-    t = int(t)
-    if t < 1:
-        raise ValueError(f"AdamW steps count from 1 (t={t})")
-    b1, b2 = float(betas[0]), float(betas[1])
-    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or lr < 0.0 or eps < 0.0 or weight_decay < 0.0:
-        raise ValueError(f"adamw_step needs lr >= 0, eps >= 0, weight_decay >= 0 and betas in [0, 1) (lr={lr}, betas={betas}, eps={eps}, "
-                         f"weight_decay={weight_decay})")
-    return _lib.NdAdamwStep(b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5, float(eps),
-                            1.0 - float(lr) * float(weight_decay))
-
-
-def _adamw_state(adamw, return_grad: bool, what: str, dev, numel: int, tensors) -> bool:
-    """Checks of a fused call's in-place tensors ((tensor, name) pairs, `numel` elements each, distinct); True when the call is fused."""
-    if adamw is None:
-        if not return_grad:
-            raise ValueError(f"{what}: adamw=None and return_grad=False: nothing to compute")
-        return False
-    if not isinstance(adamw, _lib.NdAdamwStep):
-        raise TypeError("adamw must be an ops.adamw_step(...) or None")
-    for t, name in tensors:
-        if t is None:
-            raise ValueError(f"{what}: {name} is None in a fused call")
-        _inplace(t, name)
-        if t.numel() != numel or t.device != dev:
-            raise ValueError(f"{name} has {t.numel()} elements on {t.device}; expected {numel} on {dev}")
-    if len({t.data_ptr() for t, _ in tensors}) != len(tensors):
-        raise ValueError(f"{what}: the parameter and moment tensors must be distinct")
-    return True
 
 
 def gemm_tn_adamw(dy: torch.Tensor, x: torch.Tensor, w: Optional[torch.Tensor], m: Optional[torch.Tensor], v: Optional[torch.Tensor], adamw,
@@ -1056,7 +1046,7 @@ def gemm_tn_adamw(dy: torch.Tensor, x: torch.Tensor, w: Optional[torch.Tensor], 
     (M, N), K = dy.shape, x.shape[1]
     if K < 16 or K % 16:
         raise ValueError(f"K must be a positive multiple of 16 (K={K})")
-    on = _adamw_state(adamw, return_grad, "gemm_tn_adamw", dy.device, N * K, ((w, "w"), (m, "m"), (v, "v")))
+    on = _fused_state(adamw, _lib.NdAdamwStep, return_grad, "gemm_tn_adamw", dy.device, ((w, "w", N * K), (m, "m", N * K), (v, "v", N * K)))
     g = torch.empty(N, K, dtype=torch.float32, device=dy.device) if return_grad else None
     check(_lib.load().nd_gemm_tn_adamw(ptr(dy), ptr(x), ptr(w) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N, K,
                                        float(gscale), ctypes.byref(adamw) if on else None, _stream(dy)), "nd_gemm_tn_adamw")
@@ -1079,7 +1069,7 @@ def colsum_adamw(dy: torch.Tensor, b: Optional[torch.Tensor], m: Optional[torch.
     if dy.dim() != 2 or dy.shape[0] < 1 or dy.shape[1] < 1:
         raise ValueError(f"dy is {tuple(dy.shape)}: expected [M >= 1, N >= 1]")
     M, N = dy.shape
-    on = _adamw_state(adamw, return_grad, "colsum_adamw", dy.device, N, ((b, "b"), (m, "m"), (v, "v")))
+    on = _fused_state(adamw, _lib.NdAdamwStep, return_grad, "colsum_adamw", dy.device, ((b, "b", N), (m, "m", N), (v, "v", N)))
     g = torch.empty(N, dtype=torch.float32, device=dy.device) if return_grad else None
     check(_lib.load().nd_colsum_adamw(ptr(dy), ptr(b) if on else None, ptr(m) if on else None, ptr(v) if on else None, ptr(g), M, N,
                                       float(gscale), ctypes.byref(adamw) if on else None, _stream(dy)), "nd_colsum_adamw")
@@ -1098,8 +1088,9 @@ def layernorm_wgrad_adamw(x: torch.Tensor, g: torch.Tensor, eps: float, gamma: O
     rows, dim = x.shape
     if dim < 4 or dim % 4 or dim > 2048:
         raise ValueError(f"dim must be a multiple of 4 in [4, 2048] (dim={dim})")
-    on = _adamw_state(adamw, return_grad, "layernorm_wgrad_adamw", x.device, dim,
-                      ((gamma, "gamma"), (beta, "beta"), (m_gamma, "m_gamma"), (v_gamma, "v_gamma"), (m_beta, "m_beta"), (v_beta, "v_beta")))
+    names = ("gamma", "beta", "m_gamma", "v_gamma", "m_beta", "v_beta")
+    on = _fused_state(adamw, _lib.NdAdamwStep, return_grad, "layernorm_wgrad_adamw", x.device,
+                      [(t, n, dim) for t, n in zip((gamma, beta, m_gamma, v_gamma, m_beta, v_beta), names)])
     dg = torch.empty(dim, dtype=torch.float32, device=x.device) if return_grad else None
     db = torch.empty(dim, dtype=torch.float32, device=x.device) if return_grad else None
     p = [ptr(t) if on else None for t in (gamma, beta, m_gamma, v_gamma, m_beta, v_beta)]

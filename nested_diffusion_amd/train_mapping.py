@@ -14,12 +14,12 @@ from __future__ import annotations
 import argparse
 import math
 import os
-import random
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
+from . import _trainer, ops
+from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
 from .mapping import Classifier, VisionTransformer, load_pickled
 
 MAX_BATCH = ops.LINEAR_BWD_MAX_M      # rows per training step: one nd_linear_bwd / nd_linear_wgrad_adam launch
@@ -33,12 +33,7 @@ DATASET_DEFAULTS = {
 TRAIN_DIR, VALID_DIR = "training", "validation"   # mapping/data/dataset.py:13: data_loader's defaults
 
 
-def step_lr(lr: float, epoch: int, step_size: int, gamma: float) -> float:
-    """StepLR's closed form: the rate during `epoch` (0-based) after `epoch` scheduler steps."""
-    return lr * gamma ** (epoch // step_size)
-
-
-class MappingTrainer:
+class MappingTrainer(EpochTrainer):
     """One mapping MLP (mapping/models/mlp.py Classifier: in_features -> hidden[0] -> hidden[1] -> hidden[2] -> num_classes, ReLU between)
     over the frozen prefix of `vit`, with Adam's per-layer m / v images and the step counter beside it."""
 
@@ -66,13 +61,6 @@ class MappingTrainer:
         p = self.model.p
         self.m = {k: (t.zeros_like() if isinstance(t, ops.PackedWeight) else torch.zeros_like(t)) for k, t in p.items()}
         self.v = {k: (t.zeros_like() if isinstance(t, ops.PackedWeight) else torch.zeros_like(t)) for k, t in p.items()}
-
-    @property
-    def lr(self) -> float:
-        return step_lr(self.base_lr, self.epoch, self.step_size, self.gamma)
-
-    def scheduler_step(self) -> None:
-        self.epoch += 1
 
     def features(self, images: torch.Tensor) -> torch.Tensor:
         """The frozen prefix as compute_guiding_prediction_py runs it: patch_embed, then blocks[0..mn_idx] -> [B, in_features]."""
@@ -121,57 +109,13 @@ class MappingTrainer:
     def logits(self, images: torch.Tensor) -> torch.Tensor:
         return self.model(self.features(images))
 
-    def evaluate(self, loader) -> Tuple[float, float]:
-        """(mean loss, accuracy) over a loader, forward only; one read-back at the end."""
-        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
-        correct = torch.zeros((), dtype=torch.int64, device=self.device)
-        n = 0
-        for images, labels in loader:
-            logits = self.logits(images)
-            labels = self._labels(labels, logits.shape[0])
-            _, loss, _ = ops.ensemble_xent_grad(logits[None], labels, check_labels=False)
-            loss_sum += loss.sum()
-            correct += (logits.argmax(dim=1) == labels).sum()
-            n += logits.shape[0]
-        if n == 0:
-            raise ValueError("evaluate: the loader is empty")
-        return float(loss_sum) / n, int(correct) / n
-
-    def train_epoch(self, loader) -> Tuple[float, float]:
-        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
-        correct = torch.zeros((), dtype=torch.int64, device=self.device)
-        n = 0
-        for images, labels in loader:
-            l, c = self.step(images, labels)
-            loss_sum += l
-            correct += c
-            n += images.shape[0]
-        if n == 0:
-            raise ValueError("train_epoch: the loader is empty")
-        return float(loss_sum) / n, int(correct) / n
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference's keys linear{1..4}.{weight,bias}, weights unpacked to [N, K], on the CPU."""
         return {k: (t.unpack() if isinstance(t, ops.PackedWeight) else t).detach().cpu().clone() for k, t in self.model.p.items()}
 
     def fit(self, train_loader, valid_loader, epochs: int, out_dir: str) -> dict:
-        """mapping/train_mapping.py:92-165: train epoch, validate, print the two lines, save on a strictly better validation accuracy, then
-        the scheduler step.  Returns {'best_acc', 'best_train_acc', 'saved_epochs', 'path'}."""
-        path = os.path.join(out_dir, "MLPs", f"block_{self.mn_idx}.pth")
-        best_acc, best_train_acc, saved = 0.0, 0.0, []
-        for epoch in range(int(epochs)):
-            tr_loss, tr_acc = self.train_epoch(train_loader)
-            print(f"Epoch {epoch} Train Loss: {tr_loss:.4f} Acc: {tr_acc:.4f}")
-            va_loss, va_acc = self.evaluate(valid_loader)
-            print(f"Epoch {epoch} Test Loss: {va_loss:.4f} Acc: {va_acc:.4f}")
-            if va_acc > best_acc:
-                best_acc, best_train_acc = va_acc, tr_acc
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                torch.save(self.state_dict(), path)
-                saved.append(epoch)
-            self.scheduler_step()
-        print(f"MLP {self.mn_idx} best train Acc: {best_train_acc:.4f} val Acc: {best_acc:.4f}")
-        return {"best_acc": best_acc, "best_train_acc": best_train_acc, "saved_epochs": saved, "path": path}
+        """mapping/train_mapping.py:92-165 (EpochTrainer._fit), saving <out_dir>/MLPs/block_<mn_idx>.pth."""
+        return self._fit(train_loader, valid_loader, epochs, os.path.join(out_dir, "MLPs", f"block_{self.mn_idx}.pth"), f"MLP {self.mn_idx}")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -192,16 +136,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def resolve_settings(args) -> dict:
-    """The run's hyper-parameters: the per-dataset defaults with --epochs / --batch_size / --seed applied."""
-    s = dict(DATASET_DEFAULTS[args.dataset])
-    if args.epochs is not None:
-        s["epochs"] = args.epochs
-    if args.batch_size is not None:
-        s["batch_size"] = args.batch_size
-    if not 1 <= s["batch_size"] <= MAX_BATCH:
-        raise SystemExit(f"--batch_size must be in [1, {MAX_BATCH}] (got {s['batch_size']})")
-    s["seed"] = random.randint(0, 10000) if args.seed is None else args.seed
-    return s
+    """The run's hyper-parameters: the per-dataset defaults with --epochs / --batch_size (at most MAX_BATCH) / --seed applied."""
+    return _trainer.resolve_settings(args, DATASET_DEFAULTS, MAX_BATCH)
 
 
 def make_loaders(root_dir: str, dataset: str, preprocess: str, batch_size: int, seed: int):

@@ -18,15 +18,14 @@ from __future__ import annotations
 import argparse
 import math
 import os
-import random
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib, ops
-from ._lib import check, ptr
+from . import _lib, _trainer, ops
+from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
 from .mapping import LN_EPS, VisionTransformer, load_pickled
-from .train_mapping import TRAIN_DIR, VALID_DIR, make_loaders, step_lr
+from .train_mapping import TRAIN_DIR, VALID_DIR, make_loaders
 
 # mapping/train_transformer.py:47-49, 95-97 (the two datasets this package has a loader for)
 DATASET_DEFAULTS = {
@@ -89,7 +88,7 @@ def _fresh_head(num_classes: int, embed: int, gen: torch.Generator) -> Dict[str,
     return {"head.weight": _uniform((num_classes, embed), bound, gen), "head.bias": _uniform((num_classes,), bound, gen)}
 
 
-class ViTTrainer:
+class ViTTrainer(EpochTrainer):
     """timm's VisionTransformer with AdamW's m / v for every parameter and the step counter beside it.  state_dict None: a fresh model
     (init_state_dict; **arch are its widths).  A state dict whose head has another class count gets the reference's fresh head."""
 
@@ -126,14 +125,7 @@ class ViTTrainer:
         """The fp32 tensor AdamW updates for state-dict key k."""
         return self.master[k] if k in self.master else self.vit.p[k]
 
-    @property
-    def lr(self) -> float:
-        return step_lr(self.base_lr, self.epoch, self.step_size, self.gamma)
-
-    def scheduler_step(self) -> None:
-        self.epoch += 1
-
-    def _labels(self, labels: torch.Tensor, B: int, check_range: bool) -> torch.Tensor:
+    def _labels(self, labels: torch.Tensor, B: int, check_range: bool = False) -> torch.Tensor:
         labels = torch.as_tensor(labels)
         if tuple(labels.shape) != (B,):
             raise ValueError(f"labels must be [{B}]")
@@ -151,7 +143,7 @@ class ViTTrainer:
         vit, p, grads = self.vit, self.vit.p, {}
         labels = self._labels(labels, images.shape[0], check_range)
         logits, cls_in, recs, B, N, H, W = vit._forward_recorded(images)
-        E, wT, gscale, fused = vit.embed_dim, vit._wT, 1.0 / images.shape[0], a is not None
+        E, gscale, fused = vit.embed_dim, 1.0 / images.shape[0], a is not None
 
         def gemm(k, dy, x):
             w = self._param(k)
@@ -177,47 +169,34 @@ class ViTTrainer:
         # the head: dlogits for its own parameters, dcls (= dlogits . head.weight, input_grad's kernel) for everything below
         _, loss, dlogits = ops.ensemble_xent_grad(logits[None], labels, check_labels=False)
         dlogits = dlogits[0]
-        dcls = torch.empty(B, E, dtype=torch.float32, device=self.device)
-        loss_h = torch.empty(B, dtype=torch.float32, device=self.device)
-        check(_lib.load().nd_xent_head_bwd(ptr(logits), ptr(labels), ptr(p["head.weight"]), ptr(dcls), ptr(loss_h), B, logits.shape[1], E,
-                                           ops._stream(logits)), "nd_xent_head_bwd")
+        dcls, _ = ops.xent_head_grad(logits, labels, p["head.weight"], check_labels=False)
         cls = ops.layernorm(cls_in, p["norm.weight"], p["norm.bias"], LN_EPS)
-        dcls_in = ops.layernorm_grad(cls_in, p["norm.weight"], dcls, LN_EPS)
-        # (a parameter is updated only after everything that reads it in this step has been enqueued: same stream)
-        gemm("head.weight", dlogits, cls)
-        colsum("head.bias", dlogits)
-        norm("norm", cls_in, dcls)
-        dy = torch.zeros(B, N, E, dtype=torch.float32, device=self.device)
-        dy[:, 0] = dcls_in                                    # only the cls token reaches the head
-        dy = dy.reshape(B * N, E)
-        dy_img = ops.split_rows(dy)
-        for i in reversed(range(vit.depth)):
-            r, pre = recs[i], f"blocks.{i}."
-            # VisionTransformer._block_grad's launches in its order, keeping the fp32 gradients at every Linear's output
-            dg = ops.gemm_split(dy_img, wT[pre + "mlp.fc2.weight"])
-            du, du_img = ops.gelu_grad_split(r["u"], dg, want_out=True)
-            dh2 = ops.gemm_split(du_img, wT[pre + "mlp.fc1.weight"])
-            dx2, dx2_img = ops.layernorm_grad(r["x2"], p[pre + "norm2.weight"], dh2, LN_EPS, residual=dy, want_split=True)
-            da = ops.gemm_split(dx2_img, wT[pre + "attn.proj.weight"])
-            dqkv, dqkv_img = ops.attention_grad(r["qkv"], r["o"], da, B, N, vit.num_heads, want_out=True, want_split=True)
-            dh1 = ops.gemm_split(dqkv_img, wT[pre + "attn.qkv.weight"])
-            dx, dx_img = ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh1, LN_EPS, residual=dx2, want_split=True)
+
+        def stage(i, r, dy, g):
+            """The parameter launches of one stage of the chain, issued right after its chain launches (a parameter is updated only after
+            everything that reads it in this step has been enqueued: same stream).  dy: dL/d(the stage's output)."""
+            if r is None:                                     # the top: the head and the final norm
+                gemm("head.weight", dlogits, cls)
+                colsum("head.bias", dlogits)
+                norm("norm", cls_in, dy)
+                return
+            pre = f"blocks.{i}."
             # the Linear inputs the forward did not keep in fp32
             gelu, _ = ops.gelu_split(r["u"], want_out=True)
             h2 = ops.layernorm(r["x2"], p[pre + "norm2.weight"], p[pre + "norm2.bias"], LN_EPS)
             h1 = ops.layernorm(r["x"], p[pre + "norm1.weight"], p[pre + "norm1.bias"], LN_EPS)
             gemm(pre + "mlp.fc2.weight", dy, gelu)
             colsum(pre + "mlp.fc2.bias", dy)
-            gemm(pre + "mlp.fc1.weight", du, h2)
-            colsum(pre + "mlp.fc1.bias", du)
-            norm(pre + "norm2", r["x2"], dh2)
-            gemm(pre + "attn.proj.weight", dx2, r["o"])
-            colsum(pre + "attn.proj.bias", dx2)
-            gemm(pre + "attn.qkv.weight", dqkv, h1)
-            colsum(pre + "attn.qkv.bias", dqkv)
-            norm(pre + "norm1", r["x"], dh1)
-            dy, dy_img = dx, dx_img
-            recs[i] = None
+            gemm(pre + "mlp.fc1.weight", g["du"], h2)
+            colsum(pre + "mlp.fc1.bias", g["du"])
+            norm(pre + "norm2", r["x2"], g["dh2"])
+            gemm(pre + "attn.proj.weight", g["dx2"], r["o"])
+            colsum(pre + "attn.proj.bias", g["dx2"])
+            gemm(pre + "attn.qkv.weight", g["dqkv"], h1)
+            colsum(pre + "attn.qkv.bias", g["dqkv"])
+            norm(pre + "norm1", r["x"], g["dh1"])
+
+        dy = vit._token_backward(dcls, cls_in, recs, B, N, per_block=stage)
         tokg = dy.reshape(B, N, E)
         colsum("pos_embed", dy.reshape(B, N * E))
         colsum("cls_token", tokg[:, 0].contiguous())
@@ -254,57 +233,13 @@ class ViTTrainer:
     def logits(self, images: torch.Tensor) -> torch.Tensor:
         return self.vit.forward(ops._f32(torch.as_tensor(images).to(self.device), "images"))
 
-    def evaluate(self, loader) -> Tuple[float, float]:
-        """(mean loss, accuracy) over a loader, forward only; one read-back at the end."""
-        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
-        correct = torch.zeros((), dtype=torch.int64, device=self.device)
-        n = 0
-        for images, labels in loader:
-            logits = self.logits(images)
-            labels = self._labels(labels, logits.shape[0], False)
-            _, loss, _ = ops.ensemble_xent_grad(logits[None], labels, check_labels=False)
-            loss_sum += loss.sum()
-            correct += (logits.argmax(dim=1) == labels).sum()
-            n += logits.shape[0]
-        if n == 0:
-            raise ValueError("evaluate: the loader is empty")
-        return float(loss_sum) / n, int(correct) / n
-
-    def train_epoch(self, loader) -> Tuple[float, float]:
-        loss_sum = torch.zeros((), dtype=torch.float32, device=self.device)
-        correct = torch.zeros((), dtype=torch.int64, device=self.device)
-        n = 0
-        for images, labels in loader:
-            l, c = self.step(images, labels)
-            loss_sum += l
-            correct += c
-            n += images.shape[0]
-        if n == 0:
-            raise ValueError("train_epoch: the loader is empty")
-        return float(loss_sum) / n, int(correct) / n
-
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """timm's keys in timm's shapes (the patch-embedding weight 4-D), on the CPU."""
         return {k: self._param(k).detach().cpu().clone() for k in self.vit.p}
 
     def fit(self, train_loader, valid_loader, epochs: int, out_dir: str, dataset: str) -> dict:
-        """mapping/train_transformer.py:104-172: train epoch, validate, print the two lines, save on a strictly better validation accuracy,
-        then the scheduler step.  Returns {'best_acc', 'best_train_acc', 'saved_epochs', 'path'}."""
-        path = checkpoint_path(out_dir, dataset)
-        best_acc, best_train_acc, saved = 0.0, 0.0, []
-        for epoch in range(int(epochs)):
-            tr_loss, tr_acc = self.train_epoch(train_loader)
-            print(f"Epoch {epoch} Train Loss: {tr_loss:.4f} Acc: {tr_acc:.4f}")
-            va_loss, va_acc = self.evaluate(valid_loader)
-            print(f"Epoch {epoch} Test Loss: {va_loss:.4f} Acc: {va_acc:.4f}")
-            if va_acc > best_acc:
-                best_acc, best_train_acc = va_acc, tr_acc
-                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-                torch.save(self.state_dict(), path)
-                saved.append(epoch)
-            self.scheduler_step()
-        print(f"Model vit on {dataset} best train Acc: {best_train_acc:.4f} val Acc: {best_acc:.4f}")
-        return {"best_acc": best_acc, "best_train_acc": best_train_acc, "saved_epochs": saved, "path": path}
+        """mapping/train_transformer.py:104-172 (EpochTrainer._fit), saving checkpoint_path(out_dir, dataset)."""
+        return self._fit(train_loader, valid_loader, epochs, checkpoint_path(out_dir, dataset), f"Model vit on {dataset}")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -325,15 +260,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 def resolve_settings(args) -> dict:
     """The run's hyper-parameters: the per-dataset defaults with --epochs / --batch_size / --seed applied."""
-    s = dict(DATASET_DEFAULTS[args.dataset])
-    if args.epochs is not None:
-        s["epochs"] = args.epochs
-    if args.batch_size is not None:
-        s["batch_size"] = args.batch_size
-    if s["batch_size"] < 1:
-        raise SystemExit(f"--batch_size must be at least 1 (got {s['batch_size']})")
-    s["seed"] = random.randint(0, 10000) if args.seed is None else args.seed
-    return s
+    return _trainer.resolve_settings(args, DATASET_DEFAULTS)
 
 
 def main(argv=None) -> dict:

@@ -295,6 +295,80 @@ def test_input_grad_is_still_the_chain_it_was():
     assert torch.equal(lg, logits) and torch.equal(loss2, loss) and torch.equal(want, dx) and float(dx.abs().max()) > 0.0
 
 
+def test_gradients_are_still_the_pass_they_were():
+    """ViTTrainer.gradients against its listing restated here from the operators (the launches of the gradient-only pass as they stood
+    while the trainer carried its own copy of the backward chain): bit for bit, every key, the loss and the logits.  B * N = 15 token
+    rows: one short of every 16-, 32- and 64-row tile and chunk of the chain."""
+    from nested_diffusion_amd import ops
+    trainer, vp = make_trainer(128, 2, 32)
+    g = gen(21)
+    x, labels = torch.rand(3, 3, 32, 32, generator=g), torch.randint(0, 2, (3,), generator=g)
+    grads, loss, logits = trainer.gradients(x, labels)
+    vit, p, E, heads = trainer.vit, trainer.vit.p, 128, 2
+    images, lab = x.to(DEV), labels.to(DEV)
+    lg, cls_in, recs, B, N, H, W = vit._forward_recorded(images)
+    assert (B, N) == (3, 5)
+    wT, gscale, want = vit.transposed_weights(), 1.0 / B, {}
+
+    def gemm(k, dy, inp):
+        want[k] = ops.gemm_tn_adamw(dy, inp, None, None, None, None, gscale=gscale, return_grad=True).reshape(vp[k].shape)
+
+    def colsum(k, dy):
+        want[k] = ops.colsum_adamw(dy, None, None, None, None, gscale=gscale, return_grad=True).reshape(vp[k].shape)
+
+    def norm(pre, inp, gr):
+        want[pre + ".weight"], want[pre + ".bias"] = ops.layernorm_wgrad_adamw(inp, gr, LN_EPS, None, None, None, None, None, None, None,
+                                                                               gscale=gscale, return_grad=True)
+
+    _, loss2, dlogits = ops.ensemble_xent_grad(lg[None], lab)
+    dlogits = dlogits[0]
+    dcls, _ = ops.xent_head_grad(lg, lab, p["head.weight"])
+    cls = ops.layernorm(cls_in, p["norm.weight"], p["norm.bias"], LN_EPS)
+    dcls_in = ops.layernorm_grad(cls_in, p["norm.weight"], dcls, LN_EPS)
+    gemm("head.weight", dlogits, cls)
+    colsum("head.bias", dlogits)
+    norm("norm", cls_in, dcls)
+    dy = torch.zeros(B, N, E, device=DEV)
+    dy[:, 0] = dcls_in
+    dy = dy.reshape(B * N, E)
+    dy_img = ops.split_rows(dy)
+    for i in reversed(range(2)):
+        r, pre = recs[i], f"blocks.{i}."
+        dg = ops.gemm_split(dy_img, wT[pre + "mlp.fc2.weight"])
+        du, du_img = ops.gelu_grad_split(r["u"], dg, want_out=True)
+        dh2 = ops.gemm_split(du_img, wT[pre + "mlp.fc1.weight"])
+        dx2, dx2_img = ops.layernorm_grad(r["x2"], p[pre + "norm2.weight"], dh2, LN_EPS, residual=dy, want_split=True)
+        da = ops.gemm_split(dx2_img, wT[pre + "attn.proj.weight"])
+        dqkv, dqkv_img = ops.attention_grad(r["qkv"], r["o"], da, B, N, heads, want_out=True, want_split=True)
+        dh1 = ops.gemm_split(dqkv_img, wT[pre + "attn.qkv.weight"])
+        dx, dx_img = ops.layernorm_grad(r["x"], p[pre + "norm1.weight"], dh1, LN_EPS, residual=dx2, want_split=True)
+        gelu, _ = ops.gelu_split(r["u"], want_out=True)
+        h2 = ops.layernorm(r["x2"], p[pre + "norm2.weight"], p[pre + "norm2.bias"], LN_EPS)
+        h1 = ops.layernorm(r["x"], p[pre + "norm1.weight"], p[pre + "norm1.bias"], LN_EPS)
+        gemm(pre + "mlp.fc2.weight", dy, gelu)
+        colsum(pre + "mlp.fc2.bias", dy)
+        gemm(pre + "mlp.fc1.weight", du, h2)
+        colsum(pre + "mlp.fc1.bias", du)
+        norm(pre + "norm2", r["x2"], dh2)
+        gemm(pre + "attn.proj.weight", dx2, r["o"])
+        colsum(pre + "attn.proj.bias", dx2)
+        gemm(pre + "attn.qkv.weight", dqkv, h1)
+        colsum(pre + "attn.qkv.bias", dqkv)
+        norm(pre + "norm1", r["x"], dh1)
+        dy, dy_img = dx, dx_img
+    tokg = dy.reshape(B, N, E)
+    colsum("pos_embed", dy.reshape(B, N * E))
+    colsum("cls_token", tokg[:, 0].contiguous())
+    dpatch = tokg[:, 1:].reshape(-1, E).contiguous()
+    gemm("patch_embed.proj.weight", dpatch, ops.patchify(images, 16))
+    colsum("patch_embed.proj.bias", dpatch)
+    assert sorted(want) == sorted(grads) == sorted(vp)
+    assert torch.equal(lg, logits) and torch.equal(loss2, loss)
+    for k in vp:
+        assert torch.equal(grads[k], want[k]), k
+        assert float(grads[k].abs().max()) > 0.0, k
+
+
 # ---- 8. it learns ---------------------------------------------------------------------------------------------------------------------
 def test_it_learns_eight_images():
     trainer, _ = make_trainer(128, 2, 32, seed=43)
