@@ -111,77 +111,71 @@ def _vit(model):
     return getattr(model, "vit", model)
 
 
-class Attack:
-    """attack.py's Attack(epsilon, attack_type, model): generate_attack(samples, labels) -> (adversarial images, success).
-    seed: key of the PGD random start.  first_image (generate_attack): the global index of samples[0] (its index in the dataset or test
-    stream), which keys each image's random start."""
+class _GradientDescentAttack:
+    """What foolbox's Linf and L2 gradient-descent attacks share (the loops are in the module docstring): a subclass names its table
+    (attack_type -> (foolbox class, rel_stepsize, steps, random_start)) and the two ops calls that differ, _random_start and _step."""
+
+    TABLE: dict = {}
+    _random_start = _step = None                 # staticmethod(ops.<norm>_random_start), staticmethod(ops.<norm>_step)
 
     def __init__(self, epsilon: float, attack_type: str, model, seed: int = 0):
+        self._check_type(attack_type)
+        self.epsilon, self.attack_type, self.model, self.seed = float(epsilon), attack_type, _vit(model), int(seed)
+        _, self.rel_stepsize, self.steps, self.random_start = self.TABLE[attack_type]
+        self.stepsize = self.rel_stepsize * self.epsilon
+
+    def start(self, x0: torch.Tensor, first_image: int = 0) -> torch.Tensor:
+        """The first iterate: x0, or (random_start) the family's random point of the eps-ball around x0, clipped to (0, 1)."""
+        if not self.random_start:
+            return x0
+        return self._random_start(x0, self.epsilon, self.seed, first_image, 0, *BOUNDS)
+
+    def step(self, x: torch.Tensor, x0: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """One gradient step from x (gradient on the GPU, then the family's step, projection onto the eps-ball, clip)."""
+        _, g, _ = self.model.input_grad(x, labels)
+        return self._step(x, x0, g, self.stepsize, self.epsilon, *BOUNDS)
+
+    def generate_attack(self, samples: torch.Tensor, labels: torch.Tensor, first_image: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        dev = self.model.device
+        x0 = samples.to(dev, torch.float32).contiguous()
+        labels = labels.to(dev, torch.int64).contiguous()
+        x = self.start(x0, first_image)
+        for _ in range(self.steps):
+            x = self.step(x, x0, labels)
+        adv = self._step(x, x0, None, 0.0, self.epsilon, float("-inf"), float("inf"))       # clip_perturbation
+        success = self.model.forward(adv).argmax(dim=1) != labels
+        return adv, success
+
+
+class Attack(_GradientDescentAttack):
+    """attack.py's Attack(epsilon, attack_type, model): generate_attack(samples, labels) -> (adversarial images, success).
+    seed: key of the PGD random start (clip(x0 + U[-eps, eps), 0, 1)).  first_image (generate_attack): the global index of samples[0]
+    (its index in the dataset or test stream), which keys each image's random start."""
+
+    TABLE = LINF_ATTACKS
+    _random_start, _step = staticmethod(ops.linf_random_start), staticmethod(ops.linf_step)
+
+    @staticmethod
+    def _check_type(attack_type: str) -> None:
         if attack_type in NOT_IMPLEMENTED:
             raise NotImplementedError(f"attack '{attack_type}' is not implemented by class Attack (only the Linf family: {', '.join(LINF_ATTACKS)}; "
                                       "see make_attack, L2Attack, CarliniWagner, autoattack.AutoAttack)")
         if attack_type not in LINF_ATTACKS:
             raise ValueError(f"Attacks of type {attack_type} is not supported")
-        self.epsilon, self.attack_type, self.model, self.seed = float(epsilon), attack_type, _vit(model), int(seed)
-        _, self.rel_stepsize, self.steps, self.random_start = LINF_ATTACKS[attack_type]
-        self.stepsize = self.rel_stepsize * self.epsilon
-
-    def start(self, x0: torch.Tensor, first_image: int = 0) -> torch.Tensor:
-        """The first iterate: x0, or (random_start) clip(x0 + U[-eps, eps), 0, 1)."""
-        if not self.random_start:
-            return x0
-        return ops.linf_random_start(x0, self.epsilon, self.seed, first_image, 0, *BOUNDS)
-
-    def step(self, x: torch.Tensor, x0: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """One gradient step from x (gradient on the GPU, then step, project, clip)."""
-        _, g, _ = self.model.input_grad(x, labels)
-        return ops.linf_step(x, x0, g, self.stepsize, self.epsilon, *BOUNDS)
-
-    def generate_attack(self, samples: torch.Tensor, labels: torch.Tensor, first_image: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        dev = self.model.device
-        x0 = samples.to(dev, torch.float32).contiguous()
-        labels = labels.to(dev, torch.int64).contiguous()
-        x = self.start(x0, first_image)
-        for _ in range(self.steps):
-            x = self.step(x, x0, labels)
-        adv = ops.linf_step(x, x0, None, 0.0, self.epsilon, float("-inf"), float("inf"))     # clip_perturbation
-        success = self.model.forward(adv).argmax(dim=1) != labels
-        return adv, success
 
 
-class L2Attack:
+class L2Attack(_GradientDescentAttack):
     """foolbox's L2 gradient-descent attacks ('BIM', 'L2PGD') with the surface of Attack: generate_attack(samples, labels) ->
-    (adversarial images, success); the loop is in the module docstring.  seed keys the random start of L2PGD, first_image is the global
-    index of samples[0]."""
+    (adversarial images, success); the loop is in the module docstring.  seed keys the random start of L2PGD (clip(x0 + eps * r, 0, 1), r
+    uniform in the unit ball), first_image is the global index of samples[0]."""
 
-    def __init__(self, epsilon: float, attack_type: str, model, seed: int = 0):
+    TABLE = L2_ATTACKS
+    _random_start, _step = staticmethod(ops.l2_random_start), staticmethod(ops.l2_step)
+
+    @staticmethod
+    def _check_type(attack_type: str) -> None:
         if attack_type not in L2_ATTACKS:
             raise ValueError(f"Attacks of type {attack_type} is not supported (the L2 family: {', '.join(L2_ATTACKS)})")
-        self.epsilon, self.attack_type, self.model, self.seed = float(epsilon), attack_type, _vit(model), int(seed)
-        _, self.rel_stepsize, self.steps, self.random_start = L2_ATTACKS[attack_type]
-        self.stepsize = self.rel_stepsize * self.epsilon
-
-    def start(self, x0: torch.Tensor, first_image: int = 0) -> torch.Tensor:
-        """The first iterate: x0, or (random_start) clip(x0 + eps * r, 0, 1), r uniform in the unit ball."""
-        if not self.random_start:
-            return x0
-        return ops.l2_random_start(x0, self.epsilon, self.seed, first_image, 0, *BOUNDS)
-
-    def step(self, x: torch.Tensor, x0: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        """One gradient step from x (gradient on the GPU, then normalise, step, project onto the L2 ball, clip)."""
-        _, g, _ = self.model.input_grad(x, labels)
-        return ops.l2_step(x, x0, g, self.stepsize, self.epsilon, *BOUNDS)
-
-    def generate_attack(self, samples: torch.Tensor, labels: torch.Tensor, first_image: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-        dev = self.model.device
-        x0 = samples.to(dev, torch.float32).contiguous()
-        labels = labels.to(dev, torch.int64).contiguous()
-        x = self.start(x0, first_image)
-        for _ in range(self.steps):
-            x = self.step(x, x0, labels)
-        adv = ops.l2_step(x, x0, None, 0.0, self.epsilon, float("-inf"), float("inf"))       # clip_perturbation
-        success = self.model.forward(adv).argmax(dim=1) != labels
-        return adv, success
 
 
 class CarliniWagner:

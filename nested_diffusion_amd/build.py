@@ -5,6 +5,7 @@ git-ignored but travels to the GPU box with the repo snapshot.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -14,11 +15,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnd_hip.so")
 SOURCES = ["nd_skinny_m0.hip", "nd_skinny_m1.hip", "nd_skinny_m2.hip", "nd_sampler.hip", "nd_ops.hip", "nd_vit.hip", "nd_image.hip", "nd_cond_gemm.hip", "nd_attention.hip", "nd_gemm_f32.hip",
-           "nd_conditioner.hip", "nd_rng.hip", "nd_gemm_b9.hip", "nd_persist.hip", "nd_vit_grad.hip", "nd_attack_l2.hip", "nd_square.hip", "nd_mlp_grad.hip", "nd_mlp_train.hip", "nd_vit_train.hip"]
+           "nd_conditioner.hip", "nd_rng.hip", "nd_gemm_b9.hip", "nd_persist.hip", "nd_vit_grad.hip", "nd_attack_linf.hip", "nd_attack_l2.hip", "nd_square.hip", "nd_mlp_grad.hip", "nd_mlp_train.hip", "nd_vit_train.hip"]
 # per-file flags: the large-M tile kernel keeps its accumulators in VGPRs (see nd_cond_gemm.hpp)
 EXTRA_FLAGS = {"nd_cond_gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "nd_gemm_f32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_gemm_b9.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
-HEADERS = [os.path.join(CSRC, "nd_common.hpp"), os.path.join(CSRC, "nd_cond_gemm.hpp"), os.path.join(CSRC, "nd_rng.hpp"), os.path.join(CSRC, "nd_b9.hpp"), os.path.join(CSRC, "nd_step.hpp"), os.path.join(CSRC, "nd_persist.hpp"), os.path.join(CSRC, "nd_host.hpp"), os.path.join(CSRC, "nd_optim.hpp"), os.path.join(os.path.dirname(HERE), "include", "nested_diffusion.h")]
+# every header a translation unit can include: a new one under csrc/ is a dependency of is_stale() without being listed
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(os.path.dirname(HERE), "include", "nested_diffusion.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Werror=inline-asm"]
 
 

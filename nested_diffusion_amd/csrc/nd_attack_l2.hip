@@ -17,16 +17,15 @@
 // partial; the finishing pass folds the <= 256 partials of an image with the same tree.  The shape depends on per_image alone, so a sum
 // has the same bits on every run, at every batch size and in every workgroup that finishes it.
 #include "nd_common.hpp"
-#include "nd_host.hpp"
+#include "nd_attack.hpp"
+#include "nd_philox.hpp"
 
 // every operation below is one rounded fp32 op in the listed order: a float32 restatement on the host reproduces the elementwise results
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int L2_THREADS = 256;
-
-__device__ __forceinline__ float l2_clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+constexpr int L2_THREADS = ND_ATTACK_THREADS;
 
 // the sum over the workgroup, the same bits in every thread (an xor butterfly adds the same two numbers in both partners)
 __device__ __forceinline__ float l2_block_sum(float s, float* sh) {
@@ -113,42 +112,21 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_project(const float* __restri
         const float4 a = a4[q];
         const float4 d = l2_delta(x4[q], step ? g4[q] : float4{}, a, step, alpha, inv);
         float4 r;
-        r.x = l2_clampf(a.x + d.x * f, lo, hi);
-        r.y = l2_clampf(a.y + d.y * f, lo, hi);
-        r.z = l2_clampf(a.z + d.z * f, lo, hi);
-        r.w = l2_clampf(a.w + d.w * f, lo, hi);
+        r.x = nd_clampf(a.x + d.x * f, lo, hi);
+        r.y = nd_clampf(a.y + d.y * f, lo, hi);
+        r.z = nd_clampf(a.z + d.z * f, lo, hi);
+        r.w = nd_clampf(a.w + d.w * f, lo, hi);
         o4[q] = r;
     }
 }
 
-// ---- random start: Philox4x32-10 and the Box-Muller of nd_rng.hip, restated ----------------------------------------------------------
-__device__ __forceinline__ void l2_philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ void l2_box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;       // (0, 1]
-    const float u2 = (float)b * 2.3283064365386963e-10f;                 // [0, 1]
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincospif(2.0f * u2, &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
-
+// ---- random start: Philox4x32-10 and Box-Muller (nd_philox.hpp) --------------------------------------------------------------------------
 __device__ __forceinline__ float4 l2_draw(uint32_t image, uint32_t q, uint32_t restart, uint64_t seed) {
     uint32_t c[4] = {image, q, restart, ND_L2_START_TAG};
-    l2_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    nd_philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     float4 z;
-    l2_box_muller(c[0], c[1], z.x, z.y);
-    l2_box_muller(c[2], c[3], z.z, z.w);
+    nd_box_muller(c[0], c[1], z.x, z.y);
+    nd_box_muller(c[2], c[3], z.z, z.w);
     return z;
 }
 
@@ -181,10 +159,10 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_start(const float* __restrict
     for (int q = blockIdx.x * L2_THREADS + threadIdx.x; q < quads; q += gridDim.x * L2_THREADS) {
         const float4 z = l2_draw(image, (uint32_t)q, restart, seed), a = a4[q];
         float4 r;
-        r.x = l2_clampf(a.x + eps * (z.x / sn), lo, hi);
-        r.y = l2_clampf(a.y + eps * (z.y / sn), lo, hi);
-        r.z = l2_clampf(a.z + eps * (z.z / sn), lo, hi);
-        r.w = l2_clampf(a.w + eps * (z.w / sn), lo, hi);
+        r.x = nd_clampf(a.x + eps * (z.x / sn), lo, hi);
+        r.y = nd_clampf(a.y + eps * (z.y / sn), lo, hi);
+        r.z = nd_clampf(a.z + eps * (z.z / sn), lo, hi);
+        r.w = nd_clampf(a.w + eps * (z.w / sn), lo, hi);
         o4[q] = r;
     }
 }
@@ -295,30 +273,24 @@ __global__ __launch_bounds__(L2_THREADS) void k_cw_update(float* __restrict__ de
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// B images of per_image elements: the common argument check (before any HIP call)
-int l2_check_rows(const char* what, int B, size_t per_image) {
-    if (B < 1 || B > 65535 || per_image == 0 || (per_image % 4) || per_image / 4 >= 0x7FFFFFFF)
-        return nd_set_err(ND_ERR_ARG, "%s needs 1 <= B <= 65535 and per_image %% 4 == 0 (B=%d, per_image=%zu)", what, B, per_image);
-    return ND_OK;
-}
+// the largest per_image / 4 the row check lets through: 0x7FFFFFFF itself is refused, because the start's loop runs to q <= quads
+constexpr size_t L2_MAX_QUADS = 0x7FFFFFFE;
 
 }  // namespace
 
 // workgroups (and partials) per image: a function of per_image alone; enough of them to fill the chip at B = 1
 extern "C" int nd_l2_parts(size_t per_image) {
-    const size_t per = (per_image / 4 + L2_THREADS - 1) / L2_THREADS;
-    return (int)(per > ND_L2_MAX_PARTS ? ND_L2_MAX_PARTS : (per ? per : 1));
+    return (int)nd_blocks_per_image(per_image / 4, ND_L2_MAX_PARTS);
 }
 
 extern "C" int nd_l2_step(const float* x, const float* x0, const float* grad, float* out, float* gnorm, float* dnorm, float* ws, int B,
                           size_t per_image, float alpha, float eps, float lo, float hi, void* stream) {
     if (!x || !x0 || !out || !dnorm || !ws || (grad && !gnorm)) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (l2_check_rows("l2 step", B, per_image)) return ND_ERR_ARG;
-    if (!aligned16(x) || !aligned16(x0) || !aligned16(grad) || !aligned16(out)) return nd_set_err(ND_ERR_ARG, "l2 step needs 16-byte aligned images");
-    const int quads = (int)(per_image / 4), parts = nd_l2_parts(per_image);
-    const dim3 grid((unsigned)parts, (unsigned)B), block(L2_THREADS);
+    if (int rc = nd_check_rows("l2 step", B, per_image, 65535, L2_MAX_QUADS)) return rc;
+    if (nd_misaligned(x, 15) || nd_misaligned(x0, 15) || nd_misaligned(grad, 15) || nd_misaligned(out, 15))
+        return nd_set_err(ND_ERR_ARG, "l2 step needs 16-byte aligned images");
+    const int quads = (int)(per_image / 4);
+    const dim3 grid = nd_image_grid(B, quads, ND_L2_MAX_PARTS), block(L2_THREADS);
     float *gpart = ws, *dpart = ws + (size_t)B * ND_L2_MAX_PARTS;
     hipStream_t st = (hipStream_t)stream;
     if (grad) {
@@ -335,10 +307,10 @@ extern "C" int nd_l2_step(const float* x, const float* x0, const float* grad, fl
 extern "C" int nd_l2_random_start(const float* x0, float* out, float* snorm, float* ws, int B, size_t per_image, uint64_t seed, uint32_t first_image,
                                   uint32_t restart, float eps, float lo, float hi, void* stream) {
     if (!x0 || !out || !snorm || !ws) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (l2_check_rows("l2 random start", B, per_image)) return ND_ERR_ARG;
-    if (!aligned16(x0) || !aligned16(out)) return nd_set_err(ND_ERR_ARG, "l2 random start needs 16-byte aligned images");
-    const int quads = (int)(per_image / 4), parts = nd_l2_parts(per_image);
-    const dim3 grid((unsigned)parts, (unsigned)B), block(L2_THREADS);
+    if (int rc = nd_check_rows("l2 random start", B, per_image, 65535, L2_MAX_QUADS)) return rc;
+    if (nd_misaligned(x0, 15) || nd_misaligned(out, 15)) return nd_set_err(ND_ERR_ARG, "l2 random start needs 16-byte aligned images");
+    const int quads = (int)(per_image / 4);
+    const dim3 grid = nd_image_grid(B, quads, ND_L2_MAX_PARTS), block(L2_THREADS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_l2_start_partial, grid, block, 0, st, ws, quads, seed, first_image, restart);
     HIP_CHECK(hipGetLastError());
@@ -351,9 +323,9 @@ extern "C" int nd_cw_attack_space(const float* x0, float* w0, float* xrec, size_
     if (!x0 || !w0 || !xrec) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (n == 0 || (n % 4)) return nd_set_err(ND_ERR_ARG, "cw attack space needs n %% 4 == 0, n >= 4 (n=%zu)", n);
     if (!(hi > lo)) return nd_set_err(ND_ERR_ARG, "cw attack space needs bounds lo < hi");
-    if (!aligned16(x0) || !aligned16(w0) || !aligned16(xrec)) return nd_set_err(ND_ERR_ARG, "cw attack space needs 16-byte aligned tensors");
-    const size_t n4 = n / 4, blocks = (n4 + L2_THREADS - 1) / L2_THREADS;
-    hipLaunchKernelGGL(k_cw_attack_space, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(L2_THREADS), 0, (hipStream_t)stream, x0, w0, xrec, n4,
+    if (nd_misaligned(x0, 15) || nd_misaligned(w0, 15) || nd_misaligned(xrec, 15)) return nd_set_err(ND_ERR_ARG, "cw attack space needs 16-byte aligned tensors");
+    const size_t n4 = n / 4;
+    hipLaunchKernelGGL(k_cw_attack_space, dim3(nd_blocks_per_image(n4, 8192)), dim3(L2_THREADS), 0, (hipStream_t)stream, x0, w0, xrec, n4,
                        (lo + hi) / 2.0f, (hi - lo) / 2.0f);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
@@ -362,18 +334,19 @@ extern "C" int nd_cw_attack_space(const float* x0, float* w0, float* xrec, size_
 extern "C" int nd_cw_model_space(const float* w0, const float* delta, const float* x0, const float* xrec, float* t_out, float* x_out, float* sq_rec,
                                  float* sq_x0, float* ws, int B, size_t per_image, float lo, float hi, void* stream) {
     if (!w0 || !delta || !x0 || !xrec || !t_out || !x_out || !sq_rec || !sq_x0 || !ws) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (l2_check_rows("cw model space", B, per_image)) return ND_ERR_ARG;
+    if (int rc = nd_check_rows("cw model space", B, per_image, 65535, L2_MAX_QUADS)) return rc;
     if (!(hi > lo)) return nd_set_err(ND_ERR_ARG, "cw model space needs bounds lo < hi");
     const void* ptrs[] = {w0, delta, x0, xrec, t_out, x_out};
     for (const void* p : ptrs)
-        if (!aligned16(p)) return nd_set_err(ND_ERR_ARG, "cw model space needs 16-byte aligned images");
-    const int quads = (int)(per_image / 4), parts = nd_l2_parts(per_image);
+        if (nd_misaligned(p, 15)) return nd_set_err(ND_ERR_ARG, "cw model space needs 16-byte aligned images");
+    const int quads = (int)(per_image / 4);
+    const dim3 grid = nd_image_grid(B, quads, ND_L2_MAX_PARTS);
     float *p_rec = ws, *p_x0 = ws + (size_t)B * ND_L2_MAX_PARTS;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_cw_model_space, dim3((unsigned)parts, (unsigned)B), dim3(L2_THREADS), 0, st, w0, delta, x0, xrec, t_out, x_out, p_rec, p_x0,
+    hipLaunchKernelGGL(k_cw_model_space, grid, dim3(L2_THREADS), 0, st, w0, delta, x0, xrec, t_out, x_out, p_rec, p_x0,
                        quads, (lo + hi) / 2.0f, (hi - lo) / 2.0f);
     HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_l2_finish2, dim3((unsigned)B), dim3(L2_THREADS), 0, st, p_rec, p_x0, sq_rec, sq_x0, parts);
+    hipLaunchKernelGGL(k_l2_finish2, dim3((unsigned)B), dim3(L2_THREADS), 0, st, p_rec, p_x0, sq_rec, sq_x0, (int)grid.x);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }
@@ -393,12 +366,12 @@ extern "C" int nd_cw_control(const float* logits, const int64_t* labels, const f
 extern "C" int nd_cw_update(float* delta, float* m, float* v, const float* dx, const float* x, const float* xrec, const float* t, float* best,
                             const int32_t* flags, int B, size_t per_image, float stepsize, float bc1, float bc2, float b_half, void* stream) {
     if (!delta || !m || !v || !dx || !x || !xrec || !t || (flags && !best)) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (l2_check_rows("cw update", B, per_image)) return ND_ERR_ARG;
+    if (int rc = nd_check_rows("cw update", B, per_image, 65535, L2_MAX_QUADS)) return rc;
     const void* ptrs[] = {delta, m, v, dx, x, xrec, t, best};
     for (const void* p : ptrs)
-        if (!aligned16(p)) return nd_set_err(ND_ERR_ARG, "cw update needs 16-byte aligned images");
+        if (nd_misaligned(p, 15)) return nd_set_err(ND_ERR_ARG, "cw update needs 16-byte aligned images");
     const int quads = (int)(per_image / 4);
-    hipLaunchKernelGGL(k_cw_update, dim3((unsigned)nd_l2_parts(per_image), (unsigned)B), dim3(L2_THREADS), 0, (hipStream_t)stream, delta, m, v, dx, x,
+    hipLaunchKernelGGL(k_cw_update, nd_image_grid(B, quads, ND_L2_MAX_PARTS), dim3(L2_THREADS), 0, (hipStream_t)stream, delta, m, v, dx, x,
                        xrec, t, best, flags, quads, stepsize, bc1, bc2, b_half);
     HIP_CHECK(hipGetLastError());
     return ND_OK;

@@ -12,27 +12,7 @@
 //   u1 = (x0 + 1) * 2^-32 in (0, 1], u2 = x1 * 2^-32 in [0, 1):  r = sqrt(-2 ln u1), (z0, z1) = r * (cos, sin)(2 pi u2); same for (x2, x3).
 #include "nd_rng.hpp"
 #include "nd_host.hpp"
-
-__device__ __forceinline__ void nd_philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ void nd_box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-    const float u1 = ((float)a + 1.0f) * 2.3283064365386963e-10f;       // (0, 1]: (2^32 - 1) + 1 rounds to 2^32 -> exactly 1
-    const float u2 = (float)b * 2.3283064365386963e-10f;                 // [0, 1]
-    const float r = sqrtf(-2.0f * logf(u1));
-    float s, c;
-    sincospif(2.0f * u2, &s, &c);
-    z0 = r * c;
-    z1 = r * s;
-}
+#include "nd_philox.hpp"
 
 // One thread per (member, draw, row, class-quad).  state: {seed, batch counter | first image << 32} read from the device when
 // `state` is non-null (so a replayed hipGraph sees the current values), else taken from the arguments.

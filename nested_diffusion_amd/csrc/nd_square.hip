@@ -13,30 +13,17 @@
 // Windows start at arbitrary (vh, vw) and W need not be a multiple of 4: every window access is a scalar fp32 load or store, consecutive
 // lanes on consecutive w (coalesced along a window row); nothing assumes 16-byte alignment inside an image.  A window of side s moves
 // Cin * s * s elements per image, against Cin * H * W for the whole-array formulation.
-#include "nd_host.hpp"
+#include "nd_attack.hpp"
+#include "nd_philox.hpp"
 
 // every operation below is one rounded fp32 op in the listed order: a float32 restatement on the host reproduces every array bit for bit
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SQ_THREADS = 256;
+constexpr int SQ_THREADS = ND_ATTACK_THREADS;
 constexpr int SQ_INIT_ROWS = 8;          // image rows per workgroup of the start: one Philox call serves them all
 constexpr int SQ_MAX_DIM = 4096;         // H, W: Cin * s * s <= 2^29, so a window's element counter (plus one grid stride) stays inside int
-
-__device__ __forceinline__ float sq_clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-
-// Philox4x32-10 (Salmon et al., SC'11) as in nd_rng.hip, restated
-__device__ __forceinline__ void sq_philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
 
 // grid (ceil(Cin * W / 256), ceil(H / SQ_INIT_ROWS), B): thread j = c * W + w owns column w of channel c over the workgroup's rows
 __global__ __launch_bounds__(SQ_THREADS) void k_square_init(const float* __restrict__ x0, const int64_t* __restrict__ index, float* __restrict__ x_best,
@@ -46,14 +33,14 @@ __global__ __launch_bounds__(SQ_THREADS) void k_square_init(const float* __restr
     if (j >= Cin * W) return;
     const int b = blockIdx.z, c = j / W, w = j - c * W;
     uint32_t p[4] = {(uint32_t)index[b], (uint32_t)j >> 2, restart, ND_SQUARE_INIT_TAG};
-    sq_philox4x32_10(p, (uint32_t)seed, (uint32_t)(seed >> 32));
+    nd_philox4x32_10(p, (uint32_t)seed, (uint32_t)(seed >> 32));
     const float sigma = (p[j & 3] >> 31) ? 1.0f : -1.0f;
     const float d = eps * sigma;
     const int h0 = blockIdx.y * SQ_INIT_ROWS, h1 = min(h0 + SQ_INIT_ROWS, H);
     const size_t base = ((size_t)b * Cin + c) * H * W + w;
     for (int h = h0; h < h1; ++h) {
         const size_t o = base + (size_t)h * W;
-        const float v = sq_clampf(x0[o] + d, lo, hi);
+        const float v = nd_clampf(x0[o] + d, lo, hi);
         x_best[o] = v;
         x_new[o] = v;
     }
@@ -68,7 +55,7 @@ __global__ __launch_bounds__(SQ_THREADS) void k_square_propose(const float* __re
     const int b = blockIdx.y;
     if (!(margin_min[b] > 0.0f)) return;
     uint32_t p[4] = {(uint32_t)index[b], iter, restart, ND_SQUARE_STEP_TAG};
-    sq_philox4x32_10(p, (uint32_t)seed, (uint32_t)(seed >> 32));
+    nd_philox4x32_10(p, (uint32_t)seed, (uint32_t)(seed >> 32));
     const int vh = (int)__umulhi(p[0], (uint32_t)(H - s + 1));        // (uint64(w0) * (H - s + 1)) >> 32: in [0, H - s]
     const int vw = (int)__umulhi(p[1], (uint32_t)(W - s + 1));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -83,7 +70,7 @@ __global__ __launch_bounds__(SQ_THREADS) void k_square_propose(const float* __re
         const size_t o = img + ((size_t)c * H + (vh + dh)) * W + (vw + dw);
         const float d = ((p[2] >> c) & 1u) ? two_eps : -two_eps;
         const float x = x0[o];
-        x_new[o] = sq_clampf(fminf(fmaxf(x_best[o] + d, x - eps), x + eps), lo, hi);
+        x_new[o] = nd_clampf(fminf(fmaxf(x_best[o] + d, x - eps), x + eps), lo, hi);
     }
 }
 
@@ -160,12 +147,8 @@ int sq_check_side(const char* what, int H, int W, int s) {
     return ND_OK;
 }
 
-// (blocks per image, images): the window's Cin * s * s elements in workgroups of 256, grid-stride beyond 1024 workgroups per image
-dim3 sq_window_grid(int B, int Cin, int s) {
-    const long n = (long)Cin * s * s;
-    const long per = (n + SQ_THREADS - 1) / SQ_THREADS;
-    return dim3((unsigned)(per > 1024 ? 1024 : per), (unsigned)B);
-}
+// a window's Cin * s * s elements in workgroups of 256: at most this many workgroups per image, grid-stride beyond
+constexpr unsigned SQ_MAX_BLOCKS = 1024;
 
 }  // namespace
 
@@ -186,8 +169,8 @@ extern "C" int nd_square_propose(const float* x0, const float* x_best, float* x_
     if (int rc = sq_check_image("square propose", B, Cin, H, W)) return rc;
     if (int rc = sq_check_side("square propose", H, W, s)) return rc;
     if (iter < 0) return nd_set_err(ND_ERR_ARG, "square propose needs iter >= 0 (iter=%d)", iter);
-    hipLaunchKernelGGL(k_square_propose, sq_window_grid(B, Cin, s), dim3(SQ_THREADS), 0, (hipStream_t)stream, x0, x_best, x_new, index, margin_min, win,
-                       Cin, H, W, s, (uint32_t)iter, seed, restart, eps, lo, hi);
+    hipLaunchKernelGGL(k_square_propose, nd_image_grid(B, (size_t)Cin * s * s, SQ_MAX_BLOCKS), dim3(SQ_THREADS), 0, (hipStream_t)stream, x0, x_best,
+                       x_new, index, margin_min, win, Cin, H, W, s, (uint32_t)iter, seed, restart, eps, lo, hi);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }
@@ -209,7 +192,8 @@ extern "C" int nd_square_commit(float* x_best, float* x_new, const int32_t* win,
     if (!x_best || !x_new || !win || !flags) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (int rc = sq_check_image("square commit", B, Cin, H, W)) return rc;
     if (int rc = sq_check_side("square commit", H, W, s)) return rc;
-    hipLaunchKernelGGL(k_square_commit, sq_window_grid(B, Cin, s), dim3(SQ_THREADS), 0, (hipStream_t)stream, x_best, x_new, win, flags, Cin, H, W, s);
+    hipLaunchKernelGGL(k_square_commit, nd_image_grid(B, (size_t)Cin * s * s, SQ_MAX_BLOCKS), dim3(SQ_THREADS), 0, (hipStream_t)stream, x_best, x_new,
+                       win, flags, Cin, H, W, s);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

@@ -342,7 +342,7 @@ def report(piw: torch.Tensor, var: torch.Tensor, prob_mean: torch.Tensor, vote: 
             "var_correct": o[2 + 2 * C:2 + 3 * C], "var_incorrect": o[2 + 3 * C:2 + 4 * C]}
 
 
-# ---- input gradient of the ViT and the Linf attack steps (csrc/nd_vit_grad.hip) ------------------------------------------------
+# ---- input gradient of the ViT (csrc/nd_vit_grad.hip) and the Linf attack steps (csrc/nd_attack_linf.hip) ---------------------
 def _image_or_tensor(out: torch.Tensor, osp: Optional[SplitMatrix], want_out: bool, want_split: bool):
     if want_out and want_split:
         return out, osp
@@ -507,9 +507,7 @@ def apgd_random_start(x0: torch.Tensor, index: torch.Tensor, eps: float, seed: i
     (seed, index[b], element, restart), so a row of a compacted subset draws what it draws in the full batch."""
     x0 = _f32(x0, "x0")
     B, per = _per_image(x0)
-    index = index.to(device=x0.device, dtype=torch.int64).contiguous()
-    if tuple(index.shape) != (B,):
-        raise ValueError(f"index must be [{B}] (the global image index of each row)")
+    index = _index(index, B, x0.device)
     out = torch.empty_like(x0)
     m_ws = torch.empty(B, dtype=torch.int32, device=x0.device)
     check(_lib.load().nd_apgd_random_start(ptr(x0), ptr(index), ptr(out), ptr(m_ws), B, per, int(seed) & 0xFFFFFFFFFFFFFFFF,

@@ -92,6 +92,27 @@ def test_header_and_signatures_carry_the_gradient_entry_points():
     assert "ND_LINF_START_TAG 0x41544B31u" in hdr
     from nested_diffusion_amd import build
     assert "nd_vit_grad.hip" in build.SOURCES
+    assert "nd_attack_linf.hip" in build.SOURCES
+
+
+def test_every_csrc_header_is_a_build_dependency():
+    """is_stale() looks at build.HEADERS: every header under csrc/ is in it, so a new one cannot be forgotten."""
+    from nested_diffusion_amd import build
+    csrc = os.path.join(ROOT, "nested_diffusion_amd", "csrc")
+    hpp = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    assert "nd_philox.hpp" in map(os.path.basename, hpp) and set(hpp) <= set(build.HEADERS)
+    assert os.path.join(ROOT, "include", "nested_diffusion.h") in build.HEADERS
+
+
+def test_one_philox_under_csrc():
+    """The Philox multiplier stands in exactly one file under csrc/: every random draw of the library goes through one generator."""
+    csrc = os.path.join(ROOT, "nested_diffusion_amd", "csrc")
+    holders = []
+    for f in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, f)) as fh:
+            if "d2511f53" in fh.read().lower():
+                holders.append(f)
+    assert holders == ["nd_philox.hpp"]
 
 
 def test_gradient_kernels_refuse_bad_arguments_before_any_launch():

@@ -1,4 +1,4 @@
-"""AutoAttack's APGD-CE on the GPU (nd_apgd_* in csrc/nd_vit_grad.hip, nested_diffusion_amd/autoattack.py): the random start and every
+"""AutoAttack's APGD-CE on the GPU (nd_apgd_* in csrc/nd_attack_linf.hip, nested_diffusion_amd/autoattack.py): the random start and every
 iteration's arrays bit for bit against a float32 restatement of autoattack's listing on the host, the gradients against float64 autograd
 through the oracle, run_standard_evaluation's row rules, the attacked tree end to end, the production shape and the attack's strength."""
 import os

@@ -1,4 +1,4 @@
-"""Edge cases of the three APGD-CE entry points (nd_apgd_random_start, nd_apgd_control, nd_apgd_update in csrc/nd_vit_grad.hip), each driven
+"""Edge cases of the three APGD-CE entry points (nd_apgd_random_start, nd_apgd_control, nd_apgd_update in csrc/nd_attack_linf.hip), each driven
 directly with designed inputs and no model: partial workgroups and both passes of the grid-stride loops, the batch tail of the control
 kernel, every argmax rule (ties, infinities, NaN logits), loss sequences that isolate each arm of the checkpoint rule, the wrap of
 loss_steps' row -1, all eight flag values in one batch with a step of its own per row, and control and update chained over 12 iterations.

@@ -1,5 +1,5 @@
 """Input gradient of the full ViT on the GPU (csrc/nd_vit_grad.hip, VisionTransformer.input_grad) and the Linf attacks built on it
-(nested_diffusion_amd/attack.py), against torch.autograd through the CPU oracle in float64."""
+(csrc/nd_attack_linf.hip, nested_diffusion_amd/attack.py), against torch.autograd through the CPU oracle in float64."""
 import math
 
 import numpy as np

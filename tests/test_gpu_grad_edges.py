@@ -1,4 +1,4 @@
-"""Edge shapes and production batches of the input-gradient and Linf-attack kernels (csrc/nd_vit_grad.hip) and of
+"""Edge shapes and production batches of the input-gradient and Linf-attack kernels (csrc/nd_vit_grad.hip, csrc/nd_attack_linf.hip) and of
 VisionTransformer.input_grad: the places where the kernels change behaviour (ragged query slices, the dK / dV accumulator that alone
 covers keys 192..207, every LayerNorm-backward instantiation, wide and confident heads, the grid-stride loops of the element-wise kernels)
 and the make_attacks batch of 32 ViT-B/16 images.
