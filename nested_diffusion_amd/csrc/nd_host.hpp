@@ -4,7 +4,7 @@
 #include <stdint.h>
 #include "../../include/nested_diffusion.h"
 
-// records the message nd_last_error() returns and hands `code` back (defined in nd_sampler.hip)
+// records the message nd_last_error() returns and hands `code` back (defined in nd_error.hip)
 int nd_set_err(int code, const char* fmt, ...);
 
 // (a macro: __FILE__ and __LINE__ name the call that failed)

@@ -1,6 +1,6 @@
 // nd_persist.hip -- a whole p_sample_loop (diffusion/diffusion_utils.py:133-163) as ONE kernel launch.  gfx950 only.
 //
-// The hipGraph form of the loop (csrc/nd_sampler.hip) is 3T+1 kernel nodes: head, lin2 block, lin3 + lin4 block per step, all
+// The hipGraph form of the loop (csrc/nd_sampler.hip, kernels: csrc/nd_step.hip) is 3T+1 kernel nodes: head, lin2 block, lin3 + lin4 block per step, all
 // members in every launch.  This is the same loop with no launch boundary: each member's ~51 workgroups stay on their CUs for all T
 // steps and meet only each other, at a per-member barrier after each of the three phases of a step (head | lin2 | lin3 + lin4);
 // members may be started `skew` apart.  The arithmetic is k_skinny's and k_step_head's, instruction for instruction where it

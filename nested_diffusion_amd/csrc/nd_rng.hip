@@ -61,18 +61,6 @@ __global__ void k_philox_raw(const uint32_t* __restrict__ ctr, uint32_t* __restr
     for (int j = 0; j < 4; ++j) out[4 * i + j] = c[j];
 }
 
-hipError_t nd_launch_philox_normal(float* out, const unsigned long long* state_dev, unsigned long long seed, uint32_t batch, uint32_t first,
-                                   int m0, int nm, int T, int B, int mc, int C, hipStream_t st) {
-    const size_t total = (size_t)nm * T * B * mc * ((C + 3) / 4);
-    hipLaunchKernelGGL(k_philox_normal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, state_dev, seed, batch, first, m0, nm, T, B, mc, C);
-    return hipGetLastError();
-}
-
-hipError_t nd_launch_rng_advance(unsigned long long* state_dev, hipStream_t st) {
-    hipLaunchKernelGGL(k_rng_advance, dim3(1), dim3(64), 0, st, state_dev);
-    return hipGetLastError();
-}
-
 void* nd_philox_normal_kernel() { return (void*)k_philox_normal; }
 void* nd_rng_advance_kernel() { return (void*)k_rng_advance; }
 
@@ -83,7 +71,9 @@ extern "C" int nd_philox_normal(float* out_dev, int n_members, int T, int B, int
     if (n_members < 1 || n_members > 255 || T < 1 || B < 1 || mc < 1 || mc > 65535 || C < 1 || C > 1024)
         return nd_set_err(ND_ERR_ARG, "need 1 <= n_members <= 255, 1 <= mc <= 65535, T, B >= 1, 1 <= C <= 1024 (n_members=%d, T=%d, B=%d, mc=%d, C=%d)",
                           n_members, T, B, mc, C);
-    HIP_CHECK(nd_launch_philox_normal(out_dev, nullptr, seed, batch_counter, first_image, 0, n_members, T, B, mc, C, (hipStream_t)stream));
+    hipLaunchKernelGGL(k_philox_normal, nd_philox_normal_grid(n_members, T, B, mc, C), dim3(256), 0, (hipStream_t)stream, out_dev,
+                       (const unsigned long long*)nullptr, (unsigned long long)seed, batch_counter, first_image, 0, n_members, T, B, mc, C);
+    HIP_CHECK(hipGetLastError());
     return ND_OK;
 }
 

@@ -1,5 +1,5 @@
 // nd_step.hpp -- what the kernels of one denoising step share: the per-member device record, the per-launch tensor table and the
-// pinned arithmetic of the posterior update and of the first ConditionalLinear block (csrc/nd_sampler.hip: the per-step kernels of the
+// pinned arithmetic of the posterior update and of the first ConditionalLinear block (csrc/nd_step.hip: the per-step kernels of the
 // hipGraph form; csrc/nd_persist.hip: the one-launch form of the same loop).  gfx950 only.
 //
 // Reference (file:line relative to the reference checkout): diffusion/diffusion_utils.py:54-111, diffusion/latent_model.py:173-177.
@@ -42,6 +42,20 @@ struct StepIO {             // per-launch tensors with a member-major leading st
     const float* y_in;  size_t yin_ms;     // [nm][M][C] (eps_theta entry point only)
     const float* alphas; const float* omabs;
 };
+
+#define ND_HEAD_INIT 0    // y = noise[0] + y_T_mean                       (diffusion_utils.py:139-140)
+#define ND_HEAD_UPDATE 1  // y = posterior(y, eps(t_prev), noise[i])       (diffusion_utils.py:66-92)
+#define ND_HEAD_GIVEN 2   // y = y_in (single eps_theta evaluation)
+#ifndef ND_HEAD_ROWS_COLS
+#define ND_HEAD_ROWS_COLS 512          // columns per workgroup of k_step_head_rows (a multiple of 128: 32 per wave and pass)
+#endif
+// kernel handles of csrc/nd_step.hip for hipLaunchKernel / hipGraph kernel nodes (C = y_dim in [1, ND_MAX_C]); argument lists:
+//   head (both forms): (MemberInline mi, const MemberDev* members, StepIO io, int mode, int i_step, int t_prev, int t, int B, int M, int maxM, int F, int NT, int T)
+//       256 threads; grid (ceil(F/1024), M, members), rows: (ceil(F/ND_HEAD_ROWS_COLS), ceil(M/16), members)
+//   final: (MemberInline mi, const MemberDev* members, StepIO io, int eps_only, int par_cur, int B, int M, int maxM, int NT, int T, float* eps_out, size_t eps_ms)
+//       64 threads; grid (M, 1, members)
+void* nd_step_head_kernel(int C, bool rows);
+void* nd_step_final_kernel(int C);
 
 // diffusion_utils.py:68-92 in the reference's operation order, fp32, no FMA contraction, so the
 // posterior is bit-identical to the CPU path for identical eps.

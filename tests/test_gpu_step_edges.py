@@ -1,4 +1,4 @@
-"""Edge shapes and launch-plan coverage of the reverse-diffusion step (csrc/nd_sampler.hip, csrc/nd_cond_gemm.hip, the k_skinny
+"""Edge shapes and launch-plan coverage of the reverse-diffusion step (csrc/nd_step.hip, csrc/nd_sampler.hip, csrc/nd_cond_gemm.hip, the k_skinny
 instantiations of csrc/nd_common.hpp), driven through EnsembleEngine and the C ABI with ref_cpu.init_cond_model_params members.
 
 The plan `emit_loop` follows is restated here (`cond_gemm_plan`, `step_launch`) with the CU count as a parameter and cross-checked

@@ -305,7 +305,7 @@ def check_linear_coverage(shapes):
 
 
 def slabs_reserved(D):
-    """the k-slabs `carve` (csrc/nd_sampler.hip) reserves per member for the encoder's split-K first layer."""
+    """the k-slabs `carve` (csrc/nd_handle.hip) reserves per member for the encoder's split-K first layer."""
     return D // 16 // 64 + 1
 
 

@@ -2,31 +2,19 @@
 // host program: every call below returns ND_ERR_ARG before any HIP call, so it needs no GPU.  Meant for a host-side sanitizer build
 // (CPU only, never on a GPU box); the device pass is left alone:
 //   cd nested_diffusion_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-gpu-sanitize \
-//       ../../tools/check_attack_args.hip nd_attack_linf.hip nd_attack_l2.hip nd_square.hip -o ../../tools/bin/check_attack_args
+//       ../../tools/check_attack_args.hip nd_error.hip nd_attack_linf.hip nd_attack_l2.hip nd_square.hip -o ../../tools/bin/check_attack_args
 //   ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1 ../../tools/bin/check_attack_args
-#include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include "../nested_diffusion_amd/csrc/nd_host.hpp"
 
-static char g_msg[512];
-
-// the library's definition lives in nd_sampler.hip, which is not linked here
-int nd_set_err(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 static int g_failed = 0;
 
 static void expect(int rc, const char* want, const char* call) {
-    const bool ok = rc == ND_ERR_ARG && strstr(g_msg, want);
-    printf("%s  %-28s rc=%d  \"%s\"\n", ok ? "ok  " : "FAIL", call, rc, g_msg);
+    const bool ok = rc == ND_ERR_ARG && strstr(nd_last_error(), want);
+    printf("%s  %-28s rc=%d  \"%s\"\n", ok ? "ok  " : "FAIL", call, rc, nd_last_error());
     g_failed += !ok;
-    g_msg[0] = 0;
+    nd_set_err(ND_OK, "%s", "");
 }
 
 int main() {
