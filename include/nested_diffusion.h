@@ -655,7 +655,8 @@ int nd_ensemble_xent_bwd(const float *logits_dev, const int64_t *labels_dev, flo
  *                         out[1] = workgroups over K, out[2] = workgroups over the row blocks, out[3] = row blocks per workgroup
  *                         (tests pick their shapes and sampled blocks from it).  No GPU needed.
  *   nd_bias_grad_adam     acc[n] = sum_m dy[m, n] in the order m = 0 .. M - 1, then the same listing on b, m, v [N] (g_out [N] or NULL).
- *   nd_unpack_rows        the exact inverse of nd_pack_rows for an ND_DTYPE_F32 image: dst [R, K] row-major, padding rows dropped. */
+ *   nd_unpack_rows        the exact inverse of nd_pack_rows for an ND_DTYPE_F32 image: dst [R, K] row-major, padding rows dropped
+ *                         (csrc/nd_pack.hip, beside nd_pack_rows). */
 typedef struct nd_adam_step {
     float beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, sqrt_bc2, eps;
 } nd_adam_step;

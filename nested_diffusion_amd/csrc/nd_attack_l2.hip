@@ -16,7 +16,6 @@
 // order, a workgroup folds its 256 threads by an xor-shuffle tree per wave and (w0 + w1) + (w2 + w3) over the waves, and writes one
 // partial; the finishing pass folds the <= 256 partials of an image with the same tree.  The shape depends on per_image alone, so a sum
 // has the same bits on every run, at every batch size and in every workgroup that finishes it.
-#include "nd_common.hpp"
 #include "nd_attack.hpp"
 #include "nd_philox.hpp"
 

@@ -2,7 +2,8 @@
 // classification_train_separately.py:337-340).  gfx950 only.  Built with -mllvm -amdgpu-mfma-vgpr-form
 // (nested_diffusion_amd/build.py): the score accumulators are consumed by the softmax (VALU) and fed back as MFMA operands, so
 // keeping them in AGPRs costs a v_accvgpr move per value each way.
-#include "nd_common.hpp"
+#include "nd_frag.hpp"
+#include "nd_device.hpp"
 #include "nd_b9.hpp"
 
 // RING form (the default fp32 kernel).  A workgroup is FOUR waves -- one per SIMD -- owning up to four 16-row query fragments

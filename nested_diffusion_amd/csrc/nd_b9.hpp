@@ -23,7 +23,7 @@
 // Measured (tools/ubench_bf16x9.hip, tools/ubench_ldsdma.hip): an LDS-DMA instruction occupies its wave's vector-memory path for 64
 // cycles but costs the same wave's MFMA stream ~1 cycle; in cycles the loop runs at 1.00-1.08 of its MFMAs alone.
 #pragma once
-#include "nd_common.hpp"
+#include "nd_math.hpp"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

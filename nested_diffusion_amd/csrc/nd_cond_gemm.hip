@@ -1,6 +1,7 @@
 // nd_cond_gemm.hip -- the LDS-tiled large-M ConditionalLinear kernels (design notes: nd_cond_gemm.hpp).  gfx950 only.
 // Built with -mllvm -amdgpu-mfma-vgpr-form (nested_diffusion_amd/build.py).
 #include "nd_cond_gemm.hpp"
+#include "nd_frag.hpp"
 #include "nd_b9.hpp"
 
 // which 128 x 128 tile a workgroup owns, and (slab >= 0) which k-slab of it

@@ -3,7 +3,7 @@
 // The reference's default operating point is mc_trials = 20 Monte-Carlo trials (classification_train_separately.py:770-771)
 // x batch_size 70 (configs/chest_x_ray.yml:66): M = B*mc = 1400 rows per member go through lin2 / lin3 at every step
 // (latent_model.py:178-184).  At that M the blocks are compute-bound ([M,4096] x [4096,4096] per member: arithmetic
-// intensity M/2 flop per weight byte), and the weight-streaming kernel of nd_common.hpp -- 64 rows per workgroup pass --
+// intensity M/2 flop per weight byte), and the weight-streaming kernel of nd_skinny_kernel.hpp -- 64 rows per workgroup pass --
 // would re-stream the 67 MB layer ceil(M/64) times.  This is the LDS-tiled kernel for that regime, on the SAME operands
 // (frag16-packed weights and activations, same folded gain/shift tables, same outputs), so nothing else changes.
 //
@@ -23,7 +23,8 @@
 // the remainder is cut into `split` k-slabs whose raw accumulators go to a workspace and are finished by k_cond_gemm_fixup
 // (slabs added in a fixed order: reproducible).
 #pragma once
-#include "nd_common.hpp"
+#include "nd_skinny.hpp"
+#include "nd_device.hpp"
 
 #define CG_T 128                 // tile edge (rows of W and rows of x)
 #define CG_F 8                   // 16-row fragments per tile edge

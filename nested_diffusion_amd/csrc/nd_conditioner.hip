@@ -229,7 +229,7 @@ extern "C" int nd_cond_set_mlp(nd_cond c, int i, const nd_mlp_weights* w) {
     return ND_OK;
 }
 
-#define ND_COND_MAX_BATCHED 8        // = ND_INLINE_DESCS (csrc/nd_common.hpp): members whose descriptors travel by value in one launch
+#define ND_COND_MAX_BATCHED 8        // = ND_INLINE_DESCS (csrc/nd_skinny.hpp): members whose descriptors travel by value in one launch
 #define ND_TRY(call)          \
     do {                      \
         int _rc = (call);     \

@@ -17,6 +17,7 @@
 #include "nd_b9.hpp"
 #include <cstdlib>
 #include "nd_host.hpp"
+#include "nd_device.hpp"
 
 #ifndef B9_DIRECT_STORE
 #define B9_DIRECT_STORE 0          // 1 (variant builds): fp32 outputs stored straight from the accumulators (rounds 4 - early 5)

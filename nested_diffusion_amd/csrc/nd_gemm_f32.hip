@@ -12,7 +12,7 @@
 // every memory instruction issues in the shadow of running MFMAs.
 // LDS rows are 16 floats + 8 pad: a lane's float4 (k = 4*(l>>4)..+3) is one conflict-free ds_read_b128; MFMA jj takes element jj
 // of every lane (k order permuted identically on both operands).
-#include "nd_common.hpp"
+#include "nd_math.hpp"
 
 #define GB_K 16
 #define GB_LD 24

@@ -191,14 +191,6 @@ extern "C" int nd_set_schedule(nd_handle h, const float* alphas_dev, const float
     return ND_OK;
 }
 
-void nd_launch_pack(const float* src, float* dst, int R, int K, int half, hipStream_t st) {
-    const size_t n4 = (size_t)((R + 15) / 16) * 16 * K / (half ? 8 : 4);
-    const size_t want = (n4 + 255) / 256;
-    const dim3 grid((unsigned)(want > 8192 ? 8192 : want));
-    if (half) hipLaunchKernelGGL(k_pack_rows_h, grid, dim3(256), 0, st, src, reinterpret_cast<_Float16*>(dst), R, K);
-    else hipLaunchKernelGGL(k_pack_rows, grid, dim3(256), 0, st, src, dst, R, K);
-}
-
 extern "C" int nd_load_member(nd_handle h, int k, const nd_member_weights* w, void* stream) {
     if (!h || !h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");
     if (k < 0 || k >= h->cfg.n_members) return nd_set_err(ND_ERR_ARG, "member %d out of range", k);
@@ -324,12 +316,7 @@ extern "C" int nd_member_buffer(nd_handle h, int k, int which, float* dst_dev, i
     // above 128 rows the step blocks of an fp32 handle run on frag32b3 images of h1 / h2 (bf16 matrix pipe): the live copies are
     // whichever the LAST launch over this member wrote (MemberHost::h_split), not what `rows` would pick
     if (!enc && m.h_split) return nd_join_rows(which == 1 ? m.h1s : m.h2s, dst_dev, rows, W, stream);
-    const size_t n4 = (size_t)((rows + 15) / 16) * 16 * W / 4;
-    if (h->half && which != 0)   // e0/e1/h1/h2 are GEMM operands (fp16 in that mode); xe never is
-        hipLaunchKernelGGL(k_unpack_rows_h, dim3((unsigned)((n4 / 2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const _Float16*>(src), dst_dev, rows, W);
-    else
-        hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst_dev, rows, W);
+    nd_launch_unpack(src, dst_dev, rows, W, h->half && which != 0, (hipStream_t)stream);   // e0/e1/h1/h2 are GEMM operands (fp16 in that mode); xe never is
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

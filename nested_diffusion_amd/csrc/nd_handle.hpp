@@ -1,7 +1,8 @@
 // nd_handle.hpp -- the ensemble handle as its two translation units see it: nd_handle.hip builds and loads it, nd_sampler.hip runs it.
 // Private to those two; the public face is include/nested_diffusion.h.
 #pragma once
-#include "nd_common.hpp"
+#include "nd_frag.hpp"
+#include "nd_skinny.hpp"
 #include "nd_step.hpp"
 #include "nd_host.hpp"
 
@@ -87,7 +88,6 @@ struct nd_handle_s {
 int nd_check_range(nd_handle_s* h, int m0, int nm);                    // workspace bound, members m0 .. m0+nm-1 exist and are loaded
 void nd_drop_graphs(nd_handle_s* h);                                   // after anything a recorded graph has baked in changes
 void nd_note_h_layout(nd_handle_s* h, int m0, int nm, bool split);     // MemberHost::h_split of a member range
-void nd_launch_pack(const float* src, float* dst, int R, int K, int half, hipStream_t st);   // row-major [R, K] -> frag16 / frag32h
 // nd_conditioner.hip
 int nd_guiding_prediction_first(nd_cond c, const float* images, float* logits_out, float* yhat_out, int B, int n_used, void* stream);
 unsigned long long nd_cond_serial(nd_cond c);     // changes with every change of the conditioner's state

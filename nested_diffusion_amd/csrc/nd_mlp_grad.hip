@@ -17,7 +17,7 @@
 // row's result has the same bits in any batch and on every run.
 // Rows n >= N of the image are the zero padding of nd_pack_rows; their dy operand is zero-filled in registers, never read (0 * garbage
 // would be NaN), and so are the rows m >= M of the last 16-row tile.
-#include "nd_common.hpp"
+#include "nd_frag.hpp"
 #include "nd_host.hpp"
 
 namespace {

@@ -1,9 +1,9 @@
-// nd_mlp_train.hip -- training of the mapping MLPs (include/nested_diffusion.h: nd_linear_wgrad_adam, nd_bias_grad_adam, nd_unpack_rows;
+// nd_mlp_train.hip -- training of the mapping MLPs (include/nested_diffusion.h: nd_linear_wgrad_adam, nd_bias_grad_adam;
 // the loop: nested_diffusion_amd/train_mapping.py MappingTrainer).  gfx950 only, all arithmetic fp32.
 //   k_wgrad_adam       G[N, K] = gscale * (dy[M, N]^T . x[M, K]) formed 16 x 16 tile by tile on the matrix pipe and applied to the packed
 //                      weight, first-moment and second-moment images in registers (torch 1.10 F.adam): the gradient never goes to memory
 //   k_bias_grad_adam   the same update for a bias: g[n] = gscale * sum_m dy[m, n]
-//   (nd_unpack_rows launches nd_common.hpp's k_unpack_rows)
+//   (nd_unpack_rows, the inverse of the images' packing: csrc/nd_pack.hip)
 //
 // k_wgrad_adam.  v_mfma_f32_16x16x4_f32 computes D[i][j] = sum_kk A[i][kk] B[kk][j] with lane l supplying A[i = l & 15][kk = l >> 4] and
 // B[kk = l >> 4][j = l & 15] and receiving D[i = 4 (l >> 4) + e][j = l & 15] in register e.  With A = x^T (lane l: x[4 s + (l >> 4)][k0 +
@@ -19,7 +19,7 @@
 // Rows m >= M of the last step and image rows n >= N (the zero padding of nd_pack_rows) get zero operands in registers, never read; the
 // gradient of a padding row is forced to 0 after the MFMA and its lanes skip the update, so neither a NaN in x nor eps = 0 reaches the
 // padding: it stays exactly 0.
-#include "nd_common.hpp"
+#include "nd_math.hpp"
 #include "nd_host.hpp"
 #include "nd_optim.hpp"
 
@@ -208,19 +208,6 @@ extern "C" int nd_bias_grad_adam(const float* dy, float* b, float* m, float* v, 
     const nd_adam_step av = a ? *a : nd_adam_step{};
     hipLaunchKernelGGL(k_bias_grad_adam, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, b, m, v, g_out, M, N, gscale, av,
                        a ? 1 : 0);
-    HIP_CHECK(hipGetLastError());
-    return ND_OK;
-}
-
-extern "C" int nd_unpack_rows(const void* src_packed, float* dst, int R, int K, int dtype, void* stream) {
-    if (!src_packed) return nd_set_err(ND_ERR_ARG, "unpack_rows: NULL image src_packed");
-    if (!dst) return nd_set_err(ND_ERR_ARG, "unpack_rows: NULL tensor dst");
-    if (dtype != ND_DTYPE_F32) return nd_set_err(ND_ERR_ARG, "unpack_rows: dtype must be ND_DTYPE_F32: only fp32 (frag16) images are unpacked");
-    if (R < 1 || K < 16 || K % 16) return nd_set_err(ND_ERR_ARG, "unpack_rows needs R >= 1 and K a positive multiple of 16 (R=%d, K=%d)", R, K);
-    if (nd_misaligned(src_packed, 15) || nd_misaligned(dst, 15)) return nd_set_err(ND_ERR_ARG, "unpack_rows: misaligned tensor (16 bytes)");
-    const size_t n16 = nd_packed_bytes_dt(R, K, 0) / 16, want = (n16 + 255) / 256;
-    const dim3 grid((unsigned)(want > 8192 ? 8192 : want));
-    hipLaunchKernelGGL(k_unpack_rows, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src_packed, dst, R, K);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

@@ -1,31 +1,12 @@
 // nd_ops.hip -- standalone operators: skinny Linear (mapping MLP), row softmax, ensemble aggregation.
 // gfx950 only.
-#include "nd_common.hpp"
+#include "nd_frag.hpp"
+#include "nd_skinny.hpp"
 #include "nd_cond_gemm.hpp"
 #include "nd_host.hpp"
 
-// ---- packing ---------------------------------------------------------------------------------
 static int bad_dtype(int dtype) { return dtype != ND_DTYPE_F32 && dtype != ND_DTYPE_F16; }
 static int kmul(int dtype) { return dtype == ND_DTYPE_F16 ? 32 : 16; }
-
-extern "C" size_t nd_packed_bytes(int R, int K, int dtype) {
-    if (bad_dtype(dtype) || R < 1 || K < kmul(dtype) || (K % kmul(dtype))) return 0;
-    return nd_packed_bytes_dt(R, K, dtype == ND_DTYPE_F16);
-}
-
-extern "C" int nd_pack_rows(const float* src, void* dst, int R, int K, int dtype, void* stream) {
-    if (!src || !dst) return nd_set_err(ND_ERR_ARG, "NULL tensor");
-    if (bad_dtype(dtype)) return nd_set_err(ND_ERR_ARG, "unknown dtype %d", dtype);
-    if (R < 1 || K < kmul(dtype) || (K % kmul(dtype)))
-        return nd_set_err(ND_ERR_ARG, "need R >= 1 and K a positive multiple of %d (K=%d)", kmul(dtype), K);
-    const int half = dtype == ND_DTYPE_F16;
-    const size_t n16 = nd_packed_bytes_dt(R, K, half) / 16, want = (n16 + 255) / 256;
-    const dim3 grid((unsigned)(want > 8192 ? 8192 : want));
-    if (half) hipLaunchKernelGGL(k_pack_rows_h, grid, dim3(256), 0, (hipStream_t)stream, src, (_Float16*)dst, R, K);
-    else hipLaunchKernelGGL(k_pack_rows, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, R, K);
-    HIP_CHECK(hipGetLastError());
-    return ND_OK;
-}
 
 // ---- nd_linear: mapping/models/mlp.py:25-28 ---------------------------------------------------
 extern "C" size_t nd_linear_workspace_bytes(int M, int K, int N, int dtype) {
@@ -47,8 +28,7 @@ static int linear_packed(const float* xpk, const float* wf, const float* scale, 
         SkinnyDesc sd{xpk, wf, nullptr, nullptr, nullptr, nullptr, part, K, N, 0, ND_ACT_NONE, 0};
         HIP_CHECK(nd_launch_skinny(L, sd, nullptr, 1, M, 0, st));
         SplitKEpiDesc se{part, scale, shift, out, N, L.S, act, out_packed};
-        const size_t q = (size_t)(((M + 15) / 16) * 16) * (((N + 15) / 16) * 16) / 4;
-        hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, se, (const SplitKEpiDesc*)nullptr, M, L.S);
+        nd_launch_splitk_epilogue(se, nullptr, 1, M, N, L.S, st);
     } else {
         SkinnyDesc d{xpk, wf, scale, shift, out, nullptr, nullptr, K, N, 0, act, out_packed};
         const CondGemmPlan tp = nd_cond_gemm_plan(K, N, M, 1, half);

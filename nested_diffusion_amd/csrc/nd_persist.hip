@@ -28,6 +28,8 @@
 // All workgroups of the grid must be resident at once: grid <= CU count, one workgroup per CU (by its LDS request), one process per
 // device (the deployment the multi-GPU path has anyway; ND_PERSIST=0 selects the graph form for rehearsals that share a device).
 #include "nd_persist.hpp"
+#include "nd_frag.hpp"
+#include "nd_device.hpp"
 #include <cstddef>
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

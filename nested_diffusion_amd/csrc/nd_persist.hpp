@@ -3,7 +3,7 @@
 //
 // Reference: diffusion/diffusion_utils.py:133-163 (the T-loop), diffusion/latent_model.py:173-184 (what one step evaluates).
 #pragma once
-#include "nd_common.hpp"
+#include "nd_skinny.hpp"
 #include "nd_step.hpp"
 
 // Barrier block in the handle's workspace: words g*32 and g*32 + 16 = arrival counter and generation of the launch's g-th member (a

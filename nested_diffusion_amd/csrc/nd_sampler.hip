@@ -57,9 +57,7 @@ static int encode_impl(nd_handle h, int m0, int nm, const float* x_dev, int B, v
     if (h->enc_splitk) {
         const SkinnyLaunch L = nd_skinny_launch<2>(D, H, B, nm, h->half);
         HIP_CHECK(nd_launch_skinny(L, SkinnyDesc{}, h->spk_dev + m0, nm, B, 0, st));
-        const size_t q = (size_t)(((B + 15) / 16) * 16) * H / 4;
-        hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((q + 255) / 256), 1, nm), dim3(256), 0, st, SplitKEpiDesc{},
-                           (const SplitKEpiDesc*)(h->spke_dev + m0), B, L.S);
+        nd_launch_splitk_epilogue(SplitKEpiDesc{}, h->spke_dev + m0, nm, B, H, L.S, st);
     } else {
         HIP_CHECK(launch_skinny<0>(h->descs_dev + (size_t)L_ENC0 * K + m0, D, H, B, 0, nm, h->half, st));
     }

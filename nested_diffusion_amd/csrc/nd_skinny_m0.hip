@@ -1,7 +1,6 @@
 // nd_skinny_m0.hip -- the k_skinny<..., MODE 0, ...> family: a ConditionalLinear block / a Linear layer with its folded scale, shift and activation.
-// One translation unit per MODE (the three compile side by side; nd_common.hpp explains the kernel and the launch plan).  gfx950 only.
-#define ND_SKINNY_MODE 0
-#include "nd_common.hpp"
+// One translation unit per MODE (the three compile side by side; nd_skinny_kernel.hpp explains the kernel and the launch plan).  gfx950 only.
+#include "nd_skinny_kernel.hpp"
 
 SkinnyLaunch nd_skinny_launch_m0(int K, int N, int M, int nm, int half) { return nd_skinny_launch_impl<0>(K, N, M, nm, half); }
 #ifdef ND_WG_TIMING

@@ -4,7 +4,7 @@
 // Reference path (file:line relative to the reference checkout):
 //   diffusion/diffusion_utils.py:54-111    p_sample / p_sample_t_1to0
 //   diffusion/latent_model.py:93-105,169-184  ConditionalLinear / ConditionalModel.forward
-#include "nd_common.hpp"
+#include "nd_frag.hpp"
 #include "nd_step.hpp"
 #include "nd_b9.hpp"
 

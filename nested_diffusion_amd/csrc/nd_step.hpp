@@ -4,7 +4,8 @@
 //
 // Reference (file:line relative to the reference checkout): diffusion/diffusion_utils.py:54-111, diffusion/latent_model.py:173-177.
 #pragma once
-#include "nd_common.hpp"
+#include "nd_math.hpp"
+#include "nd_skinny.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // device-side member record (everything the head / final kernels need)

@@ -1,7 +1,8 @@
 // nd_vit.hip -- kernels for the ViT prefix of the mapping network (timm 0.4.12 vit_base_patch16_224
 // semantics; call sites classification_train_separately.py:337-340).  gfx950 only, fp32 with
 // f32-input MFMA (exact f32 products).
-#include "nd_common.hpp"
+#include "nd_math.hpp"
+#include "nd_device.hpp"
 #include "nd_b9.hpp"
 #include "nd_host.hpp"
 #include <cstdlib>
@@ -242,7 +243,7 @@ extern "C" int nd_gemm_bias_act(const float* x, const void* w, const float* bias
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the last dim; one wave per row, two-pass (mean, then centred variance) in registers (nd_ln_stats,
-// nd_common.hpp).
+// nd_math.hpp).
 // ---------------------------------------------------------------------------------------------
 // SPLIT: the result is written as a frag32b3 image (csrc/nd_b9.hpp) -- the input form of the Linear layer that follows every
 // LayerNorm of a ViT block -- instead of fp32 row-major: a lane's 4 consecutive columns are three 8-byte pieces.

@@ -13,7 +13,8 @@
 //   k_xent_head_bwd     softmax(logits) - onehot(label) times head.weight; per-image cross-entropy
 //   k_margin_head_bwd   Carlini & Wagner's head: the gradient of c * max(0, logit margin) times head.weight; margin and runner-up
 //   k_unpatchify        inverse permutation of k_patchify (stride == kernel: no overlap)
-#include "nd_common.hpp"
+#include "nd_math.hpp"
+#include "nd_device.hpp"
 #include "nd_b9.hpp"
 #include "nd_host.hpp"
 

@@ -22,7 +22,7 @@
 // Summation order of k_colsum_adamw and k_ln_wgrad_partial / _finish (ND_COLSUM_CHUNK = 64): the rows are cut into chunks of 64 (the last one
 // shorter); a chunk's partial is p = 0, p += term(r) for r in row order; the result is acc = 0, acc += p in chunk order.  A function of
 // the row count alone: not of the width, the grid or which wave summed a chunk.
-#include "nd_common.hpp"
+#include "nd_math.hpp"
 #include "nd_host.hpp"
 #include "nd_optim.hpp"
 

@@ -1,5 +1,5 @@
 """Edge cases of the mapping-MLP gradient and training kernels (csrc/nd_mlp_grad.hip: nd_linear_bwd, nd_ensemble_xent_bwd;
-csrc/nd_mlp_train.hip: nd_linear_wgrad_adam, nd_bias_grad_adam, nd_unpack_rows) and of MappingTrainer's loss head:
+csrc/nd_mlp_train.hip: nd_linear_wgrad_adam, nd_bias_grad_adam; csrc/nd_pack.hip: nd_unpack_rows) and of MappingTrainer's loss head:
 
 - the ensemble head element by element against the float64 closed form, over both sides of its stride-64 and stride-256 loops and uneven
   member counts, under a bound counted from the kernel's operations; confident logits up to a margin of 110; one member underflowing

@@ -427,7 +427,7 @@ def test_linear_four_and_five_row_fragments_with_up_to_six_weight_fragments(dtyp
 
 
 def test_gelu_exact_erf_accuracy_through_an_identity_gemm():
-    """timm's Mlp uses the exact-erf GELU (fc1 epilogue).  nd_erf is a branch-free < 1 ulp erf (csrc/nd_common.hpp); a GEMM against the
+    """timm's Mlp uses the exact-erf GELU (fc1 epilogue).  nd_erf is a branch-free < 1 ulp erf (csrc/nd_math.hpp); a GEMM against the
     identity (exact products, exact sums) exposes it element by element: against torch in fp64 the error stays within fp32 rounding of
     the three steps (argument product, erf, 1 + erf) -- absolute 2e-7 max(1, |v|) -- over [-9, 9], denormal-small and large arguments."""
     from nested_diffusion_amd import ops

@@ -1,5 +1,5 @@
 """Edge shapes and launch-plan coverage of the reverse-diffusion step (csrc/nd_step.hip, csrc/nd_sampler.hip, csrc/nd_cond_gemm.hip, the k_skinny
-instantiations of csrc/nd_common.hpp), driven through EnsembleEngine and the C ABI with ref_cpu.init_cond_model_params members.
+instantiations of csrc/nd_skinny_kernel.hpp), driven through EnsembleEngine and the C ABI with ref_cpu.init_cond_model_params members.
 
 The plan `emit_loop` follows is restated here (`cond_gemm_plan`, `step_launch`) with the CU count as a parameter and cross-checked
 against nd_step_plan / nd_skinny_plan for every shape used (tests/test_abi_and_host.py runs the same restatement at 256 CUs without a

@@ -1,5 +1,5 @@
-"""Edge shapes and launch-plan coverage of the weight-streaming Linear (k_skinny MODE 0 / MODE 2 and k_splitk_epilogue of
-csrc/nd_common.hpp, linear_packed / nd_pack_rows of csrc/nd_ops.hip), of the encoder hoist (nd_encode of csrc/nd_sampler.hip, with the
+"""Edge shapes and launch-plan coverage of the weight-streaming Linear (k_skinny MODE 0 / MODE 2 of csrc/nd_skinny_kernel.hpp, k_splitk_epilogue
+of csrc/nd_skinny_m2.hip, linear_packed of csrc/nd_ops.hip, nd_pack_rows of csrc/nd_pack.hip), of the encoder hoist (nd_encode of csrc/nd_sampler.hip, with the
 k_fold_bn folds of nd_load_member) and of the mapping MLP that runs on the same stream (Classifier, GuidingConditioner).
 
 The launch plan is restated here (`skinny_plan` from nd_skinny_launch_impl, `linear_route` from nd_use_splitk / nd_cond_gemm_plan) with
@@ -78,7 +78,7 @@ def cdiv(a, b):
 
 # ---- 1. the launch plan, restated ------------------------------------------------------------------------------------------------
 def skinny_plan(K, N, M, nm, half, mode, ncu):
-    """nd_skinny_launch_impl (csrc/nd_common.hpp): geometry, kernel instantiation, load policy and LDS form of one k_skinny launch."""
+    """nd_skinny_launch_impl (csrc/nd_skinny_kernel.hpp): geometry, kernel instantiation, load policy and LDS form of one k_skinny launch."""
     mt = pick_mt(M)
     nfr, nch = cdiv(N, 16), (K // 32 if half else K // 16)
     mtiles, mgroups = cdiv(M, 16), cdiv(M, 16 * mt)

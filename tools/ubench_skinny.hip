@@ -5,7 +5,7 @@
 // interleaved rounds in one process, median + min reported as GB/s of weight bytes.
 #include <hip/hip_runtime.h>
 #define ND_WG_TIMING
-#include "../nested_diffusion_amd/csrc/nd_common.hpp"
+#include "../nested_diffusion_amd/csrc/nd_skinny_kernel.hpp"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -707,7 +707,11 @@ void launch4(P p, int G, hipStream_t st) {
     hipLaunchKernelGGL((k_var4<MT, NF, WAVES, NT>), grid, dim3(WAVES * 64), 0, st, p, G);
 }
 
-// ---- the library's own kernel (nd_common.hpp), driven through its launch helper ----
+// ---- the library's own kernel (nd_skinny_kernel.hpp), driven through its launch helper ----
+// (this one-file build instantiates the three families the library keeps in csrc/nd_skinny_m{0,1,2}.hip)
+SkinnyLaunch nd_skinny_launch_m0(int K, int N, int M, int nm, int half) { return nd_skinny_launch_impl<0>(K, N, M, nm, half); }
+SkinnyLaunch nd_skinny_launch_m1(int K, int N, int M, int nm, int half) { return nd_skinny_launch_impl<1>(K, N, M, nm, half); }
+SkinnyLaunch nd_skinny_launch_m2(int K, int N, int M, int nm, int half) { return nd_skinny_launch_impl<2>(K, N, M, nm, half); }
 static SkinnyDesc* g_tab = nullptr;   // [3][G]: MODE0 packed out, MODE1 projection, MODE0 row-major out
 static int g_G = 0, g_M = 0, g_K = 0, g_N = 0;
 template <int MODE, int WHICH>
