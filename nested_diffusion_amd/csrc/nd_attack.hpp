@@ -15,11 +15,7 @@ inline int nd_check_rows(const char* what, int B, size_t per_image, int max_B, s
     return ND_OK;
 }
 
-// workgroups per image: ceil(items / 256), at least 1, at most cap (grid-stride beyond)
-inline unsigned nd_blocks_per_image(size_t items, unsigned cap) {
-    const size_t per = (items + ND_ATTACK_THREADS - 1) / ND_ATTACK_THREADS;
-    return (unsigned)(per > cap ? cap : (per ? per : 1));
-}
-
-// (workgroups per image, images): every workgroup belongs to one image; enough of them to fill the chip at B = 1
+// (workgroups per image, images): every workgroup belongs to one image; enough of them (nd_blocks_per_image, nd_host.hpp) to fill
+// the chip at B = 1
+static_assert(ND_ATTACK_THREADS == 256, "nd_blocks_per_image counts in workgroups of 256");
 inline dim3 nd_image_grid(int B, size_t items, unsigned cap) { return dim3(nd_blocks_per_image(items, cap), (unsigned)B); }

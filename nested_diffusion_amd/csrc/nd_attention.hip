@@ -1,10 +1,13 @@
-// nd_attention.hip -- the fp32 attention core of the ViT blocks (timm 0.4.12 Attention.forward, head dim 64; call sites
-// classification_train_separately.py:337-340).  gfx950 only.  Built with -mllvm -amdgpu-mfma-vgpr-form
+// nd_attention.hip -- the attention core of the ViT blocks (timm 0.4.12 Attention.forward, head dim 64; call sites
+// classification_train_separately.py:337-340): the entry points of all three forms (at the end) and the two fp32 kernels, RING and
+// bf16 x 9; the fp16-operand kernel is nd_attention_h.hip.  gfx950 only.  Built with -mllvm -amdgpu-mfma-vgpr-form
 // (nested_diffusion_amd/build.py): the score accumulators are consumed by the softmax (VALU) and fed back as MFMA operands, so
 // keeping them in AGPRs costs a v_accvgpr move per value each way.
 #include "nd_frag.hpp"
 #include "nd_device.hpp"
 #include "nd_b9.hpp"
+#include "nd_host.hpp"
+#include "nd_vit.hpp"
 
 // RING form (the default fp32 kernel).  A workgroup is FOUR waves -- one per SIMD -- owning up to four 16-row query fragments
 // of one (image, head): ceil(NF/4) workgroups per head (NF = 13 at N = 196: 4 + 3 + 3 + 3 fragments), 1536 workgroups at
@@ -583,12 +586,9 @@ static hipError_t launch_attention_b9(const void* att, float* out, int B, int N,
 }
 
 hipError_t nd_launch_attention_b9(const void* att, float* out, int B, int N, int heads, int split_out, hipStream_t st) {
-    switch ((N + 15) / 16) {
-#define AB_CASE(NFV) case NFV: return launch_attention_b9<NFV>(att, out, B, N, heads, split_out, st);
-        AB_CASE(1) AB_CASE(2) AB_CASE(3) AB_CASE(4) AB_CASE(5) AB_CASE(6) AB_CASE(7) AB_CASE(8)
-        AB_CASE(9) AB_CASE(10) AB_CASE(11) AB_CASE(12) AB_CASE(13) AB_CASE(14) AB_CASE(15) AB_CASE(16)
-#undef AB_CASE
-    }
+#define AB_LAUNCH(NFV) return launch_attention_b9<NFV>(att, out, B, N, heads, split_out, st)
+    ND_DISPATCH_NF((N + 15) / 16, AB_LAUNCH)
+#undef AB_LAUNCH
     return hipErrorInvalidValue;
 }
 
@@ -602,11 +602,48 @@ static hipError_t launch_attention_ring(const float* qkv, float* out, int B, int
 }
 
 hipError_t nd_launch_attention_ring(const float* qkv, float* out, int B, int N, int heads, int split_out, hipStream_t st) {
-    switch ((N + 15) / 16) {
-#define AR_CASE(NFV) case NFV: return launch_attention_ring<NFV>(qkv, out, B, N, heads, split_out, st);
-        AR_CASE(1) AR_CASE(2) AR_CASE(3) AR_CASE(4) AR_CASE(5) AR_CASE(6) AR_CASE(7) AR_CASE(8)
-        AR_CASE(9) AR_CASE(10) AR_CASE(11) AR_CASE(12) AR_CASE(13) AR_CASE(14) AR_CASE(15) AR_CASE(16)
-#undef AR_CASE
-    }
+#define AR_LAUNCH(NFV) return launch_attention_ring<NFV>(qkv, out, B, N, heads, split_out, st)
+    ND_DISPATCH_NF((N + 15) / 16, AR_LAUNCH)
+#undef AR_LAUNCH
     return hipErrorInvalidValue;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Attention core for d = 64:  out = softmax(q k^T / 8) v per (image, head), q/k/v read from the fused qkv activations.
+// MFMA operand maps shared by the fp32 RING kernel above and the fp16-operand kernel (nd_attention_h.hip):
+//   S^T = K Q^T   : A = K[key=16f+(l&15)][d=16c+4g+jj], B = Q[q=l&15][same d]  -> D[key=16f+4g+r][q=l&15]
+//   softmax over keys: in-lane over (f, r), across the 4 lane groups g by xor 16/32.
+//   O^T = V^T P^T : the k-step (f, r) takes key 16f+4g+r from lane group g -- exactly the S^T register acc[f][r] of that
+//                   lane -- and A = V[key][4*(l&15)+e] (float4, e = d-frag), so P needs no transpose.  D_e[i=4g'+r'][q]: d = 4*i + e.
+// ---------------------------------------------------------------------------------------------
+static int attention_any(const float* qkv, float* out, int B, int N, int heads, int d, int dtype, int split_out, void* stream) {
+    if (!qkv || !out) return nd_set_err(ND_ERR_ARG, "NULL tensor");
+    if (d != 64) return nd_set_err(ND_ERR_ARG, "head dim must be 64 (got %d)", d);
+    if (nd_bad_dtype(dtype)) return nd_set_err(ND_ERR_ARG, "unknown dtype %d", dtype);
+    if (B < 1 || heads < 1 || N < 1 || N > 16 * AT_MAXF) return nd_set_err(ND_ERR_ARG, "need 1 <= N <= %d", 16 * AT_MAXF);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == ND_DTYPE_F16) HIP_CHECK(nd_launch_attention_h(qkv, out, B, N, heads, st));
+    else HIP_CHECK(nd_launch_attention_ring(qkv, out, B, N, heads, split_out, st));
+    HIP_CHECK(hipGetLastError());
+    return ND_OK;
+}
+
+extern "C" int nd_attention(const float* qkv, float* out, int B, int N, int heads, int d, int dtype, void* stream) {
+    return attention_any(qkv, out, B, N, heads, d, dtype, 0, stream);
+}
+
+// the fp32 attention with its result written as the frag32b3 image of [B*N, heads*64]: the input of the proj nd_gemm_split
+extern "C" int nd_attention_split(const float* qkv, void* out_split, int B, int N, int heads, int d, void* stream) {
+    return attention_any(qkv, (float*)out_split, B, N, heads, d, ND_DTYPE_F32, 1, stream);
+}
+
+// The attention core on the bf16 matrix pipe with exact fp32 products (k_attention_b9): operands = the qkv images nd_gemm_split_qkv wrote.
+// out_dev: fp32 [B*N, heads*64] (out_is_split == 0) or the frag32b3 image of that matrix (the input of the proj nd_gemm_split).
+extern "C" int nd_attention_images(const void* qkv_images, void* out, int out_is_split, int B, int N, int heads, void* stream) {
+    if (!qkv_images || !out) return nd_set_err(ND_ERR_ARG, "NULL tensor");
+    if (B < 1 || heads < 1 || N < 1) return nd_set_err(ND_ERR_ARG, "bad B / N / heads");
+    if (!nd_qkv_images_supported(N, heads)) return nd_set_err(ND_ERR_ARG, "qkv images need N %% 4 == 0, N <= 256, heads * 64 %% 128 == 0 (N=%d, heads=%d)", N, heads);
+    if (((uintptr_t)qkv_images | (uintptr_t)out) & 15) return nd_set_err(ND_ERR_ARG, "tensors must be 16-byte aligned");
+    HIP_CHECK(nd_launch_attention_b9(qkv_images, (float*)out, B, N, heads, out_is_split ? 1 : 0, (hipStream_t)stream));
+    return ND_OK;
 }

@@ -33,6 +33,12 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 // bytes of the frag32b3 image of an [R][K] matrix
 static inline size_t nd_b9_bytes(int R, int K) { return (size_t)((R + 15) / 16) * (K / 32) * B9_BLOCK_UNITS * 16; }
 
+// grid of the kernels that walk such an image with one thread per 8-value run, i.e. one wave per block: 256 threads per workgroup
+static inline dim3 nd_b9_image_grid(int rows, int K) {
+    const long nb = (long)((rows + 15) / 16) * (K / 32);
+    return dim3((unsigned)((nb * 64 + 255) / 256));
+}
+
 // the three bf16 pieces of one fp32 value (exact: a == (float)h1 + (float)h2 + (float)h3 for every finite a whose pieces do not
 // underflow, i.e. |a| > 2^-110 or a == 0).  An infinite a (or one that rounds to an infinite bf16) keeps h1 = +-inf and zero low
 // pieces, so that it multiplies like an infinity (inf - inf would make the low pieces NaN); a NaN stays a NaN.

@@ -1,5 +1,6 @@
 // nd_conditioner.hip -- the mapping network as ONE C-level call (gfx950 only): host-side sequencing of the ViT and
-// mapping-MLP kernels of nd_vit.hip / nd_gemm_f32.hip / nd_attention.hip / nd_ops.hip.
+// mapping-MLP kernels (ViT: nd_patchify.hip, nd_layernorm.hip, nd_gemm_nt.hip / nd_gemm_f32.hip / nd_gemm_b9.hip, nd_attention.hip /
+// nd_attention_h.hip; mapping MLPs: nd_linear.hip; the conditions' softmax: nd_report.hip).
 //
 // Reference (file:line relative to the reference checkout):
 //   diffusion/classification_train_separately.py:249-275   cond_pred_model = {'vit', 'mlps'} (whole-module pickles)
@@ -14,16 +15,7 @@
 #include <cstring>
 #include <cstdlib>
 #include "nd_host.hpp"
-
-// nd_ops.hip: Classifier.forward on packed activations (one input pack, hidden layers written in streaming order)
-int nd_mlp_chain(const float* x, const void* const* wpk, const float* const* bias, const int* dims, float* const* hid, float* logits,
-                 int M, int dtype, void* ws, size_t ws_bytes, void* stream);
-// ... and the same with layers 2..4 of several MLPs sharing launches (their first layers run one by one, each behind its prefix block)
-bool nd_mlp_tail_batchable(const int* dims, int M, int nm, int dtype);
-int nd_mlp_chain_first(const float* x, const void* w1pk, const float* bias1, const int* dims, float* hid0, int M, int dtype, void* ws,
-                       size_t ws_bytes, void* stream);
-int nd_mlp_chain_tail(int nm, const nd_mlp_weights* w, const int* dims, float* const* hid0, float* const* hid1, float* const* hid2, float* logits,
-                      size_t logits_stride, int M, int dtype, void* stream);
+#include "nd_linear.hpp"
 
 static std::atomic<unsigned long long> g_cond_serial{1};
 
@@ -77,6 +69,11 @@ static int check_cfg(const nd_cond_config* c) {
 
 static inline size_t zmax(size_t a, size_t b) { return a > b ? a : b; }
 
+// does an ND_DTYPE_F32_SPLIT block at N tokens run the image attention (k_attention_b9 on the qkv images)?  Not at a token count the
+// image form does not take (the full forward's 197: N % 4 != 0), and not under ND_ATT_F32=1, read at every call: when the workspace
+// is carved and at every block.
+static bool image_attention_at(const nd_cond_config& g, int N) { return nd_qkv_images_supported(N, g.num_heads) && !getenv("ND_ATT_F32"); }
+
 // carve with base == nullptr computes the size only
 static void carve(nd_cond_s* c, char* base, size_t* total) {
     const nd_cond_config& g = c->cfg;
@@ -98,9 +95,8 @@ static void carve(nd_cond_s* c, char* base, size_t* total) {
         c->xs = take(nd_split_bytes((int)R, (int)(kpe > E ? kpe : E)));
         c->fc1s = take(nd_split_bytes((int)R, (int)Hd));
         // the attention's operand images (92 MB at B = 32, 196 tokens, 12 heads) only where a block can use them: the prefix blocks run
-        // at the patch count `ntok`; a token count the image form does not take (the full forward's 197: N % 4 != 0) or ND_ATT_F32=1
-        // keeps the fp32 qkv buffer above and reserves nothing here
-        c->qkv_img_tokens = (nd_qkv_images_supported((int)ntok, g.num_heads) && !getenv("ND_ATT_F32")) ? (int)ntok : 0;
+        // at the patch count `ntok`; where image_attention_at says no, the fp32 qkv buffer above serves and nothing is reserved here
+        c->qkv_img_tokens = image_attention_at(g, (int)ntok) ? (int)ntok : 0;
         c->qkv_img = c->qkv_img_tokens ? take(nd_qkv_images_bytes((int)B, c->qkv_img_tokens, g.num_heads)) : nullptr;
     } else {
         c->fc1 = (float*)take(R * Hd * 4);
@@ -244,7 +240,7 @@ static int vit_block(nd_cond_s* c, int block, const float* tin, float* tout, int
         // the same block with the four Linear layers on the bf16 matrix pipe, exact fp32 products (csrc/nd_b9.hpp): the weights are
         // frag32b3 images, every GEMM input is written as one by its producer (LayerNorm, attention and the fc1 epilogue)
         ND_TRY(nd_layernorm_split(tin, w.norm1_w, w.norm1_b, c->xs, R, E, g.ln_eps, st));
-        if (c->qkv_img && N <= c->qkv_img_tokens && nd_qkv_images_supported(N, g.num_heads) && !getenv("ND_ATT_F32")) {
+        if (c->qkv_img && N <= c->qkv_img_tokens && image_attention_at(g, N)) {
             // attention on the bf16 matrix pipe too: the qkv Linear writes q, k and v^T as the MFMA operand images of the attention kernel
             ND_TRY(nd_gemm_split_qkv(c->xs, w.qkv_w, w.qkv_b, c->qkv_img, B, N, g.num_heads, E, st));
             ND_TRY(nd_attention_images(c->qkv_img, c->xs, 1, B, N, g.num_heads, st));

@@ -357,8 +357,7 @@ extern "C" int nd_split_rows(const float* x_dev, void* out_dev, int rows, int K,
     if (!x_dev || !out_dev) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (rows < 1 || K < 32 || (K % 32)) return nd_set_err(ND_ERR_ARG, "need rows >= 1 and K a positive multiple of 32 (K=%d)", K);
     if (((uintptr_t)x_dev | (uintptr_t)out_dev) & 15) return nd_set_err(ND_ERR_ARG, "tensors must be 16-byte aligned");
-    const long nb = (long)((rows + 15) / 16) * (K / 32);
-    hipLaunchKernelGGL(k_b9_split_rows, dim3((unsigned)((nb * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, (bf16x8*)out_dev, rows, K);
+    hipLaunchKernelGGL(k_b9_split_rows, nd_b9_image_grid(rows, K), dim3(256), 0, (hipStream_t)stream, x_dev, (bf16x8*)out_dev, rows, K);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }
@@ -366,8 +365,7 @@ extern "C" int nd_split_rows(const float* x_dev, void* out_dev, int rows, int K,
 extern "C" int nd_join_rows(const void* in_dev, float* x_dev, int rows, int K, void* stream) {
     if (!x_dev || !in_dev) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (rows < 1 || K < 32 || (K % 32)) return nd_set_err(ND_ERR_ARG, "need rows >= 1 and K a positive multiple of 32 (K=%d)", K);
-    const long nb = (long)((rows + 15) / 16) * (K / 32);
-    hipLaunchKernelGGL(k_b9_join_rows, dim3((unsigned)((nb * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)in_dev, x_dev, rows, K);
+    hipLaunchKernelGGL(k_b9_join_rows, nd_b9_image_grid(rows, K), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)in_dev, x_dev, rows, K);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

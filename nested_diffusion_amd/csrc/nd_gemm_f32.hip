@@ -13,9 +13,7 @@
 // LDS rows are 16 floats + 8 pad: a lane's float4 (k = 4*(l>>4)..+3) is one conflict-free ds_read_b128; MFMA jj takes element jj
 // of every lane (k order permuted identically on both operands).
 #include "nd_math.hpp"
-
-#define GB_K 16
-#define GB_LD 24
+#include "nd_vit.hpp"      // GB_K, GB_LD: shared with the plan of nd_gemm_nt.hip
 
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, const float* __restrict__ w,
@@ -174,7 +172,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, co
     }
 }
 
-// 128 x 64 tiles (GT_BM x GT_BN of nd_vit.hip); grid = whole tiles + remainder tiles x split
+// 128 x 64 tiles (GT_BM x GT_BN of nd_gemm_nt.hip); grid = whole tiles + remainder tiles x split
 hipError_t nd_launch_gemm_nt_128x64(const float* x, const float* w, const float* bias, const float* res, float* out, int M, int K, int N,
                                     int act, int n_full, int split, float* part, unsigned grid, hipStream_t st) {
     hipLaunchKernelGGL((k_gemm_nt<128, 64>), dim3(grid), dim3(256), 0, st, x, w, bias, res, out, M, K, N, act, n_full, split, part);

@@ -15,6 +15,16 @@ int nd_set_err(int code, const char* fmt, ...);
             return nd_set_err(ND_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// operand dtype of the Linear / GEMM / attention entry points, and the K multiple of its MFMA (16x16x4 f32, 16x16x32 f16)
+inline int nd_bad_dtype(int dtype) { return dtype != ND_DTYPE_F32 && dtype != ND_DTYPE_F16; }
+inline int nd_kmul(int dtype) { return dtype == ND_DTYPE_F16 ? 32 : 16; }
+
+// workgroups of 256 threads for `items` work items: ceil(items / 256), at least 1, at most cap (grid-stride beyond)
+inline unsigned nd_blocks_per_image(size_t items, unsigned cap) {
+    const size_t per = (items + 255) / 256;
+    return (unsigned)(per > cap ? cap : (per ? per : 1));
+}
+
 inline bool nd_misaligned(const void* p, uintptr_t mask) { return ((uintptr_t)p & mask) != 0; }
 
 // true when two of the non-NULL pointers are the same buffer

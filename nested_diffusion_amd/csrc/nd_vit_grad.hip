@@ -17,6 +17,7 @@
 #include "nd_device.hpp"
 #include "nd_b9.hpp"
 #include "nd_host.hpp"
+#include "nd_vit.hpp"
 
 // Every product below is rounded to fp32 before it is used: no contraction into a following add (in particular not into the first
 // subtraction of nd_b9_split, which would make a frag32b3 image differ from the split of the fp32 value stored beside it).
@@ -24,7 +25,7 @@
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm backward, one wave per row: dx = rstd * (gg - mean(gg) - xh * mean(gg * xh)) (+ res), gg = g * gamma, xh = (x - mean) * rstd.
-// The statistics are recomputed exactly as k_layernorm (nd_vit.hip) computes them (nd_ln_stats).
+// The statistics are recomputed exactly as k_layernorm (nd_layernorm.hip) computes them (nd_ln_stats).
 // ---------------------------------------------------------------------------------------------
 template <int VPL>
 __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ g,
@@ -425,11 +426,6 @@ __global__ __launch_bounds__(256) void k_unpatchify(const float* __restrict__ co
 // ---------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------
-static unsigned grid_for(size_t n) {
-    const size_t b = (n + 255) / 256;
-    return (unsigned)(b > 8192 ? 8192 : (b ? b : 1));
-}
-
 extern "C" int nd_layernorm_bwd(const float* x, const float* gamma, const float* g, const float* residual, float* out, void* out_split,
                                 int rows, int dim, float eps, void* stream) {
     if (!x || !gamma || !g || (!out && !out_split)) return nd_set_err(ND_ERR_ARG, "NULL tensor");
@@ -439,11 +435,9 @@ extern "C" int nd_layernorm_bwd(const float* x, const float* gamma, const float*
     const dim3 grid((rows + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;
     bf16x8* os = reinterpret_cast<bf16x8*>(out_split);
-    if (vpl <= 1) hipLaunchKernelGGL((k_layernorm_bwd<1>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps);
-    else if (vpl <= 2) hipLaunchKernelGGL((k_layernorm_bwd<2>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps);
-    else if (vpl <= 3) hipLaunchKernelGGL((k_layernorm_bwd<3>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps);
-    else if (vpl <= 4) hipLaunchKernelGGL((k_layernorm_bwd<4>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps);
-    else hipLaunchKernelGGL((k_layernorm_bwd<8>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps);
+#define LNB_LAUNCH(V) hipLaunchKernelGGL((k_layernorm_bwd<V>), grid, block, 0, st, x, gamma, g, residual, out, os, rows, dim, eps)
+    ND_DISPATCH_VPL(vpl, LNB_LAUNCH);
+#undef LNB_LAUNCH
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }
@@ -451,8 +445,7 @@ extern "C" int nd_layernorm_bwd(const float* x, const float* gamma, const float*
 static int gelu_any(const float* u, const float* dg, float* out, void* out_split, int rows, int cols, bool bwd, void* stream) {
     if (!u || !out_split || (bwd && !dg)) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (rows < 1 || cols < 32 || (cols % 32)) return nd_set_err(ND_ERR_ARG, "gelu images need cols %% 32 == 0 (cols=%d)", cols);
-    const long nb = (long)((rows + 15) / 16) * (cols / 32);
-    const dim3 grid((unsigned)((nb * 64 + 255) / 256));
+    const dim3 grid = nd_b9_image_grid(rows, cols);
     if (bwd) hipLaunchKernelGGL((k_gelu_split<true>), grid, dim3(256), 0, (hipStream_t)stream, u, dg, out, reinterpret_cast<bf16x8*>(out_split), rows, cols);
     else hipLaunchKernelGGL((k_gelu_split<false>), grid, dim3(256), 0, (hipStream_t)stream, u, dg, out, reinterpret_cast<bf16x8*>(out_split), rows, cols);
     HIP_CHECK(hipGetLastError());
@@ -502,7 +495,7 @@ extern "C" int nd_unpatchify(const float* cols, float* img, int B, int Cin, int 
     if (!cols || !img) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     if (B < 1 || Cin < 1 || p < 4 || (p % 4) || Himg % p || Wimg % p) return nd_set_err(ND_ERR_ARG, "patch size must be a multiple of 4 dividing the image");
     const size_t total4 = (size_t)B * Cin * Himg * Wimg / 4;
-    hipLaunchKernelGGL(k_unpatchify, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)stream, cols, img, B, Cin, Himg, Wimg, p);
+    hipLaunchKernelGGL(k_unpatchify, dim3(nd_blocks_per_image(total4, 8192)), dim3(256), 0, (hipStream_t)stream, cols, img, B, Cin, Himg, Wimg, p);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

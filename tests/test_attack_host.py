@@ -104,6 +104,15 @@ def test_every_csrc_header_is_a_build_dependency():
     assert os.path.join(ROOT, "include", "nested_diffusion.h") in build.HEADERS
 
 
+def test_every_csrc_unit_is_a_build_source():
+    """build.SOURCES is exactly the *.hip files under csrc/, and every per-unit flag of build.EXTRA_FLAGS names one of them: a renamed
+    unit cannot be left out of the library or silently lose its flag."""
+    from nested_diffusion_amd import build
+    hip = {f for f in os.listdir(os.path.join(ROOT, "nested_diffusion_amd", "csrc")) if f.endswith(".hip")}
+    assert hip == set(build.SOURCES) and len(build.SOURCES) == len(hip)
+    assert set(build.EXTRA_FLAGS) <= set(build.SOURCES)
+
+
 def test_one_philox_under_csrc():
     """The Philox multiplier stands in exactly one file under csrc/: every random draw of the library goes through one generator."""
     csrc = os.path.join(ROOT, "nested_diffusion_amd", "csrc")

@@ -1,5 +1,5 @@
 """Edge shapes and launch-plan coverage of the weight-streaming Linear (k_skinny MODE 0 / MODE 2 of csrc/nd_skinny_kernel.hpp, k_splitk_epilogue
-of csrc/nd_skinny_m2.hip, linear_packed of csrc/nd_ops.hip, nd_pack_rows of csrc/nd_pack.hip), of the encoder hoist (nd_encode of csrc/nd_sampler.hip, with the
+of csrc/nd_skinny_m2.hip, linear_packed of csrc/nd_linear.hip, nd_pack_rows of csrc/nd_pack.hip), of the encoder hoist (nd_encode of csrc/nd_sampler.hip, with the
 k_fold_bn folds of nd_load_member) and of the mapping MLP that runs on the same stream (Classifier, GuidingConditioner).
 
 The launch plan is restated here (`skinny_plan` from nd_skinny_launch_impl, `linear_route` from nd_use_splitk / nd_cond_gemm_plan) with
@@ -133,7 +133,7 @@ def cond_gemm_plan(K, N, M, nm, half, ncu):
 
 
 def linear_route(K, N, M, half, ncu):
-    """linear_packed (csrc/nd_ops.hip): 'splitk' (k_skinny MODE 2 + k_splitk_epilogue) from K = 16384, else 'tile' (k_cond_gemm) above
+    """linear_packed (csrc/nd_linear.hip): 'splitk' (k_skinny MODE 2 + k_splitk_epilogue) from K = 16384, else 'tile' (k_cond_gemm) above
     128 fp32 rows, else 'stream' (k_skinny MODE 0); with the launch plan of the streaming forms and the workspace nd_linear asks for."""
     el = 2 if half else 4
     packed = cdiv(M, 16) * 16 * K * el

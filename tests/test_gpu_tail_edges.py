@@ -1,5 +1,5 @@
 """Edge shapes of the kernels on either side of the sampler: aggregation and row softmax (k_aggregate, k_softmax_rows), the reporting
-tail (k_sample_stats, k_report; csrc/nd_ops.hip), the five image kernels (csrc/nd_image.hip) and the in-library noise (k_philox_normal;
+tail (k_sample_stats, k_report; csrc/nd_report.hip), the five image kernels (csrc/nd_image.hip) and the in-library noise (k_philox_normal;
 csrc/nd_rng.hip).  The argument rejections of the same operators are in tests/test_tail_host.py (no GPU needed).
 
 What this covers

@@ -1,5 +1,5 @@
 """Edge shapes and launch-plan coverage of the ViT forward kernels: the fp32 GEMM on the bf16 pipe (nd_gemm_split, csrc/nd_gemm_b9.hip)
-and the f32-MFMA / fp16 GEMM (nd_gemm_bias_act, csrc/nd_vit.hip) at every branch of their tile plans, the qkv-image GEMM, the three
+and the f32-MFMA / fp16 GEMM (nd_gemm_bias_act, csrc/nd_gemm_nt.hip) at every branch of their tile plans, the qkv-image GEMM, the three
 attention forms, LayerNorm in both output forms and patchify.
 
 The two tile plans are restated here (`b9_plan`, `gemm_plan`) with the device's CU count; every shape the tests use is cross-checked
@@ -65,7 +65,7 @@ def b9_plan(M, K, N):
 
 
 def gemm_plan(M, K, N, dtype):
-    """nd_gemm_plan (csrc/nd_vit.hip): (split, workspace bytes).  128 x 64 tiles, one per CU per round; when M N K >= 2^28 the
+    """nd_gemm_plan (csrc/nd_gemm_nt.hip): (split, workspace bytes).  128 x 64 tiles, one per CU per round; when M N K >= 2^28 the
     tiles % CUs remainder is cut into s in {1, .., 6, 8} k-slabs, the smallest s within 10 % of the shortest tail."""
     bk = 32 if dtype == F16 else 16
     tiles = -(-M // 128) * -(-N // 64)

@@ -1,4 +1,4 @@
-"""Argument rejections of the aggregation, report, image and noise operators (csrc/nd_ops.hip, csrc/nd_image.hip, csrc/nd_rng.hip).
+"""Argument rejections of the aggregation, report, image and noise operators (csrc/nd_report.hip, csrc/nd_image.hip, csrc/nd_rng.hip).
 Every one is decided on the host before any launch, so this runs without a GPU: the tensor arguments are small dummy non-NULL
 addresses that are never dereferenced.  Each call must return nonzero and leave a message in nd_last_error() that names the
 offending argument with the value it had (the keyword beside each case).  The limits are the
