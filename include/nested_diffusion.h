@@ -2,7 +2,8 @@
  * nested_diffusion.h -- C ABI of libnd_hip.so, the MI355X (gfx950) implementation of the
  * nested-diffusion (LaDiNE) inference hot path, of the attacks on it, and of the training steps of the
  * mapping MLPs and of the ViT (the weight gradient and Adam / AdamW fused into one pass over the weight:
- * "training of the mapping MLPs" and "training of the ViT" below).  Training of the noise estimators is not implemented.
+ * "training of the mapping MLPs" and "training of the ViT" below), and of the training step of the noise estimators (BatchNorm in
+ * training mode forward and backward, gradient-norm clipping and Adam from materialised gradients: "training of the noise estimators").
  *
  * The reference (xingbpshen/nested-diffusion) has no FFI: its hot path is plain Python calling
  * torch ops.  Each entry point below therefore names the reference Python call(s) it replaces
@@ -719,6 +720,82 @@ int nd_layernorm_wgrad_adamw(const float *x_dev, const float *g_dev, float *gamm
                              float *m_beta_dev, float *v_beta_dev, float *g_out_gamma_dev, float *g_out_beta_dev, int rows, int dim, float eps,
                              float gscale, const nd_adamw_step *a, void *ws_dev, size_t ws_bytes, void *stream);
 size_t nd_layernorm_wgrad_workspace_bytes(int rows, int dim);
+
+/* ---- training of the noise estimators (csrc/nd_diffusion_train.hip; the loop: train_diffusion.py NoiseEstimatorTrainer; replaces
+ * noise_estimator(...) in train mode, loss.backward(), clip_grad_norm_ and optimizer.step() of
+ * diffusion/classification_train_separately.py:967-1006 for latent_model.py's ConditionalModel, arch 'linear').  The Linear layers run on
+ * nd_linear, nd_linear_bwd and the gradient-only mode of nd_linear_wgrad_adam / nd_bias_grad_adam above; these entry points are what the
+ * model has beyond them.  fp32 row-major data.  None of them allocates, copies synchronously or synchronises; no atomics; every loop is
+ * bounded by the shape arguments; the same bits on every run.  Each line of nd_qsample, nd_mse_grad, nd_sumsq and nd_clip_adam is one
+ * rounded fp32 operation, no contraction, division and square root correctly rounded; the optimizer listing is nd_linear_wgrad_adam's
+ * (csrc/nd_optim.hpp), not a second copy.  The two BatchNorm entry points read and write fp32 and carry a column's statistics and sums
+ * in DOUBLE, rounding once where a value is stored (torch's CPU BatchNorm accumulates float data in double too): with few rows that
+ * nearly coincide rstd approaches 1 / sqrt(eps) and the backward cancels, and an all-fp32 chain was measured at twelve times torch's error.
+ *   nd_bn_train_fwd   ConditionalLinear's gain (latent_model.py:103-104), nn.BatchNorm1d in training mode, the activation and the product
+ *                     y = x * y of latent_model.py:177, for u [M, N] = the Linear's output.  One thread owns a column and walks its rows
+ *                     r = 0 .. M - 1 in order (M <= 128 makes a reduction across threads pointless; the accesses are coalesced across
+ *                     columns).  v is an fp32 product, as torch's separate multiply gives it; the lines after it are double:
+ *                         v = fp32(table[t[r]][n] * u[r][n])             (table [rows_table, N], t [M] int32; both NULL: v = u)
+ *                         mean = (sum_r v) / M
+ *                         var = (sum_r (v - mean) * (v - mean)) / M      (two passes)
+ *                         rstd = 1 / sqrt(var + eps)
+ *                         xhat = fp32((v - mean) * rstd)
+ *                         z = fp32((xhat * gamma[n]) + beta[n])
+ *                         a = softplus(z) (ND_ACT_SOFTPLUS: nd_linear's fp32 softplus, threshold 20) or z (ND_ACT_NONE)
+ *                         out = a * mul[r][n]                            (fp32; mul [M, N] or NULL: out = a)
+ *                     writes out [M, N], xhat [M, N], rstd [N] = fp32(rstd); running_mean / running_var [N], when not NULL, are updated
+ *                     in place as torch does: rm = fp32(((1 - mom) * rm) + (mom * mean)), rv = fp32(((1 - mom) * rv) + (mom * (var * (M /
+ *                     (M - 1))))).  2 <= M <= ND_LINEAR_BWD_MAX_M (M = 1 is ND_ERR_ARG: torch raises there too), N >= 1 with no
+ *                     alignment demand.  A row whose t[r] lies outside [0, rows_table) reads no table row: its v is 0.
+ *   nd_bn_train_bwd   the gradient of all of that, given dout [M, N] = dL/dout and the forward's u, xhat, rstd (the fp32 values it
+ *                     stored).  Per column, rows in order, z and a recomputed from xhat, gamma, beta exactly as the forward does; the
+ *                     sums and dv in double, every output rounded to fp32 once:
+ *                         da = dout * mul                                (or dout);   dmul = fp32 dout * a   (written when dmul != NULL)
+ *                         dz = da * (1 / (1 + exp(-z)))                  (softplus with z <= 20; otherwise dz = da)
+ *                         dgamma = sum_r dz * xhat;   dbeta = sum_r dz
+ *                         dv = (gamma * rstd) * ((dz - (dbeta / M)) - (xhat * (dgamma / M)))
+ *                         du = dv * table[t[r]][n];   dtable[t[r]][n] = fp32(dtable[t[r]][n] + (dv * u))   (without gain: du = dv)
+ *                     dtable [rows_table, N] is the DENSE gradient of the embedding table (nn.Embedding is not sparse here: Adam moves
+ *                     every row on every step); the entry point zeroes it on the stream first, and a column's owner adds the rows that
+ *                     share a timestep in row order: deterministic.  A row whose t[r] lies outside [0, rows_table) reads and writes
+ *                     no table row (du = 0 there).  Outputs are distinct buffers and none of them an input.
+ *   nd_qsample        q_sample (diffusion_utils.py:39-50) with PER-ROW coefficients the host gathered from its schedule tables (no
+ *                     device-side indexing by t): yt = ((ca[r] * y0) + ((1 - ca[r]) * yhat)) + (cb[r] * e); y0, yhat, e, yt [M, C].
+ *   nd_mse_grad       loss[0] = (sum_i (e[i] - out[i])^2) / (M * C), i in row-major order from 0 (one thread), and
+ *                     dout = (out - e) * (2 / (M * C)): (e - out).square().mean() and its gradient.  C <= ND_MSE_MAX_C.
+ *   nd_sumsq          acc[0] = sum_i x[i] * x[i] (accumulate != 0: added to acc[0]) over n floats, two stages through ws_dev
+ *                     (nd_sumsq_workspace_bytes(n), overwritten).  The order is a function of n alone: x is cut into chunks of
+ *                     ND_SUMSQ_CHUNK; in a chunk, thread j of 256 forms p = 0, p += x[k] * x[k] for k = chunk start + j + 256 i,
+ *                     i = 0 .. 15 (elements past n skipped); the 256 values are added as s[j] += s[j + h] for h = 128, 64 .. 1; the
+ *                     chunk totals go to ws.  Then thread j forms p = 0, p += ws[c] for c = j, j + 256, ..., the same tree follows, and
+ *                     acc[0] = acc[0] + total (or total).  clip_grad_norm_ takes the norm of the per-tensor norms; summing the squares
+ *                     of every tensor into one scalar and taking ONE square root is the same number up to rounding.
+ *   nd_sumsq_plan     out[0] = chunks, out[1] = the longest serial chain of additions of that order (tests bound the error by it).  No GPU.
+ *   nd_clip_adam      clip_grad_norm_'s scaling and torch.optim.Adam on materialised gradients, elementwise over n floats of w, m, v, g
+ *                     (any layout: nd_pack_rows images and row-major tensors alike; the zero padding of an image stays 0 for eps > 0):
+ *                         total = sqrt(sumsq[0])
+ *                         c = max_norm / (total + 1e-6)
+ *                         coef = (c < 1) ? c : 1                         (a NaN gives 1, as torch 1.10's `if clip_coef < 1`)
+ *                         g' = g * coef
+ *                     then nd_linear_wgrad_adam's listing on (w, m, v, g').  sumsq == NULL: no clipping (g' = g). */
+#define ND_SUMSQ_CHUNK 4096
+#define ND_SUMSQ_MAX_N ((size_t)1 << 40)
+#define ND_MSE_MAX_C 1024
+int nd_bn_train_fwd(const float *u_dev, const float *table_dev, const int32_t *t_dev, int rows_table, const float *mul_dev,
+                    const float *gamma_dev, const float *beta_dev, float *out_dev, float *xhat_dev, float *rstd_dev, float *running_mean_dev,
+                    float *running_var_dev, int M, int N, int act, float eps, float momentum, void *stream);
+int nd_bn_train_bwd(const float *dout_dev, const float *u_dev, const float *table_dev, const int32_t *t_dev, int rows_table,
+                    const float *mul_dev, const float *xhat_dev, const float *rstd_dev, const float *gamma_dev, const float *beta_dev,
+                    float *du_dev, float *dmul_dev, float *dgamma_dev, float *dbeta_dev, float *dtable_dev, int M, int N, int act,
+                    void *stream);
+int nd_qsample(const float *y0_dev, const float *yhat_dev, const float *e_dev, const float *ca_dev, const float *cb_dev, float *yt_dev, int M,
+               int C, void *stream);
+int nd_mse_grad(const float *out_dev, const float *e_dev, float *dout_dev, float *loss_dev, int M, int C, void *stream);
+int nd_sumsq(const float *x_dev, size_t n, float *acc_dev, int accumulate, void *ws_dev, size_t ws_bytes, void *stream);
+int nd_sumsq_plan(size_t n, size_t *out2);
+size_t nd_sumsq_workspace_bytes(size_t n);
+int nd_clip_adam(float *w_dev, float *m_dev, float *v_dev, const float *g_dev, size_t n, const float *sumsq_dev, float max_norm,
+                 const nd_adam_step *a, void *stream);
 
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */

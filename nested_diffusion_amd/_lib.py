@@ -202,6 +202,14 @@ SIGNATURES = {
     "nd_layernorm_wgrad_adamw": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, C.POINTER(NdAdamwStep), _vp, _sz, _vp]),
     "nd_layernorm_wgrad_workspace_bytes": (_sz, [_i, _i]),
     "nd_report": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "nd_bn_train_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    "nd_bn_train_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_qsample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "nd_mse_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "nd_sumsq": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp]),
+    "nd_sumsq_plan": (_i, [_sz, C.POINTER(_sz)]),
+    "nd_sumsq_workspace_bytes": (_sz, [_sz]),
+    "nd_clip_adam": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, C.POINTER(NdAdamStep), _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

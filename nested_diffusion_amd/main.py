@@ -4,8 +4,9 @@
         --doc chest_x_ray --preprocess grayscaled --ni [--device N] [--timesteps T] [--seed S] [--exp DIR] ...
 
 Same flags, YAML keys and checkpoint layout as the reference (main.py:16-161, 166-296, 299-380;
-canonical invocation testing_scripts/test.sh:24).  Only `--test` with loss card_onehot_conditional and
-aux_cls.arch == 'sevit' (the shipped configs) and `--calib` are implemented; training / sampling flags are
+canonical invocation testing_scripts/test.sh:24).  Implemented, with loss card_onehot_conditional and
+aux_cls.arch == 'sevit' (the shipped configs): `--test`, `--calib`, and -- with neither -- training of the noise
+estimator `--mlp_idx` on one GPU (runner.Diffusion.train); the other training / sampling flags are
 parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N -m nested_diffusion_amd.main ...`.
 """
@@ -195,7 +196,10 @@ def main(argv=None) -> int:
             print("Optimal t value: {:.4f}".format(res.x[0]))
             procedure = "Testing"
         else:
-            raise NotImplementedError("training is outside the accelerated hot path")
+            if args.mlp_idx is None:
+                raise ValueError("training needs --mlp_idx: the mapping MLP whose prediction conditions the noise estimator (-1: the ViT)")
+            runner.train(mlp_idx=args.mlp_idx)                       # main.py:363-365
+            procedure = "Training"
         logging.info("\n{} procedure finished. It took {:.4f} minutes.\n\n\n".format(procedure, (time.time() - start_time) / 60))
     except Exception:
         logging.error(traceback.format_exc())                     # main.py:377-378: logged, exit code stays 0 ...

@@ -2,7 +2,7 @@
 diffusion/classification_train_separately.py -- __init__ schedule block (:215-226), conditioner
 loading (:249-275), compute_guiding_prediction (:330-348), convert_to_prob (:392-398),
 compute_ensemble_confidence (:425-447), majority_voting_for_mc_samples (:51-68) and the hot loop
-of test_atk (:749-794), plus the report metrics and test_calibrate.  Training and attacks are out of scope.
+of test_atk (:749-794), plus the report metrics and test_calibrate, and train (:842-1141) for one noise estimator.
 
 Host code is PyTorch plumbing; every tensor operation of the hot path runs in libnd_hip.so.
 """
@@ -151,6 +151,107 @@ class Diffusion(object):
         if self._seeded_first != first_image:
             self.engine.seed(self.seed or 0, first_image=first_image)
             self._seeded_first = first_image
+
+    # ---- training of one noise estimator (:842-1141) ---------------------------------------------
+    def train(self, mlp_idx: int, train_loader=None, valid_loader=None) -> dict:
+        """Diffusion.train (:842-1141) for the noise estimator conditioned on mapping MLP `mlp_idx` (-1: on the full ViT's output), on ONE
+        GPU: per step the learning rate of lr_at (when optim.lr_schedule is set), the antithetic timestep draw, the conditioner's
+        softmax as yhat, e = randn, and one train_diffusion.NoiseEstimatorTrainer.step (q_sample, the model in train mode, the
+        mean-squared error, backward, clip_grad_norm_, Adam).  Every training.validation_freq epochs and on the last one the
+        validation set is sampled with the current weights (p_sample_loop in eval mode: trainer.state_dict() loaded into a one-member
+        EnsembleEngine, noise drawn in the library) and the top-1 accuracy of y_0 taken; a new best writes
+        <log_path>/diffu{idx}_ckpt_best_eph{epoch}_acc{acc:.4f}.pth = {'noise_estimator', 'optimizer', 'epoch'}, the layout
+        load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: nothing reads it (the reference's resume path is
+        commented out, :890-908), and Adam's moments of the 150528 x 4096 layer would triple the file.  No EMA shadow is kept: the
+        reference updates one and never reads it.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
+        (default: <dataroot>/training shuffled in batches of training.batch_size, <dataroot>/validation in batches of
+        testing.batch_size, drop_last).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
+        from .train_diffusion import NoiseEstimatorTrainer, antithetic_timesteps, cast_label_to_one_hot_and_prototype, lr_at
+        args, config = self.args, self.config
+        K = len(self.cond_pred_model.mlps)
+        if not -1 <= mlp_idx < K:
+            raise NotImplementedError(f"mlp_idx must be -1 (the ViT's output) or in [0, {K}) (mlp_idx={mlp_idx})")
+        _, world = nd_dist.rank_world()
+        if world > 1:
+            raise NotImplementedError("Diffusion.train runs on one GPU: world size > 1 is not implemented")
+        if getattr(args, "train_guidance_only", False):
+            raise NotImplementedError("--train_guidance_only is not implemented")
+        if getattr(args, "resume_training", False):
+            raise NotImplementedError("--resume_training is not implemented (the reference's resume path is commented out)")
+        if config.diffusion.aux_cls.arch != "sevit":
+            raise NotImplementedError(f"aux_cls.arch == {config.diffusion.aux_cls.arch!r}: only 'sevit' is implemented")
+        if self.operand_dtype != "f32":
+            raise NotImplementedError("training runs in fp32 mode: the fp16 mode is not implemented")
+        print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
+        B_valid = config.testing.batch_size
+        if train_loader is None or valid_loader is None:
+            from .data import ImageFolderDataset
+            workers = int(getattr(config.data, "num_workers", 0) or 0)
+            if train_loader is None:
+                ds = ImageFolderDataset(os.path.join(config.data.dataroot, "training"), config.data.dataset, args.preprocess)
+                train_loader = torch.utils.data.DataLoader(ds, batch_size=config.training.batch_size, shuffle=True, num_workers=workers)
+            if valid_loader is None:
+                ds = ImageFolderDataset(os.path.join(config.data.dataroot, "validation"), config.data.dataset, args.preprocess)
+                valid_loader = torch.utils.data.DataLoader(ds, batch_size=B_valid, shuffle=False, num_workers=workers, drop_last=True)
+        trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0)
+        engine: Optional[EnsembleEngine] = None
+        n_epochs, freq = config.training.n_epochs, config.training.validation_freq
+        log_freq = getattr(config.training, "logging_freq", 0) or 0
+        max_accuracy, step, best = 0.0, 0, None
+        losses, accuracies = [], {}
+
+        def yhat_of(images):
+            logits = self.compute_guiding_prediction(images, include_full_vit=mlp_idx == -1)
+            return ops.softmax_rows(logits[mlp_idx].contiguous())            # :955-958
+
+        for epoch in range(n_epochs):
+            loss = None
+            for i, (x_raw, labels) in enumerate(train_loader):
+                x = x_raw.to(self.device, torch.float32).contiguous()
+                y0, _ = cast_label_to_one_hot_and_prototype(labels, config, return_prototype=False)
+                if config.optim.lr_schedule:
+                    trainer.lr = lr_at(i / len(train_loader) + epoch, config)     # :927-928
+                n = x.shape[0]
+                step += 1
+                t = antithetic_timesteps(n, self.num_timesteps)                   # :945-948, on the CPU
+                yhat = yhat_of(x)
+                e = torch.randn(n, config.data.num_classes, dtype=torch.float32, device=self.device)    # :965
+                loss, _ = trainer.step(torch.flatten(x, 1), y0.to(self.device), yhat, t, e)
+                if log_freq and (step % log_freq == 0 or step == 1):
+                    logging.info(f"During epoch: {epoch}, step: {step}, Noise Estimation loss: {loss.item()}")
+            if loss is None:
+                raise ValueError("the training loader is empty")
+            losses.append(float(loss))
+            logging.info(f"epoch: {epoch}, step: {step}, Noise Estimation loss: {losses[-1]}")
+            if epoch % freq == 0 or epoch + 1 == n_epochs:                        # :1054-1055
+                if engine is None:
+                    engine = EnsembleEngine(config.data.num_classes, config.model.data_dim, config.model.hidden_dim, config.model.feature_dim,
+                                            self.num_timesteps, n_members=1, max_batch=B_valid, max_rows=B_valid, device=self.device)
+                    engine.set_schedule(self.alphas, self.one_minus_alphas_bar_sqrt)
+                    engine.seed(self.seed or 0)
+                engine.load_member(0, trainer.state_dict(cpu=False))
+                acc_sum, n_batches = 0.0, 0
+                for images_raw, target in valid_loader:
+                    images = images_raw.to(self.device, torch.float32).contiguous()
+                    yhat = yhat_of(images)
+                    engine.encode(torch.flatten(images, 1))
+                    y_0 = engine.sample(yhat[None], yhat[None], None, mc=1, T=self.num_timesteps, use_graph=False)[0]   # :1103-1108
+                    acc_sum += float((y_0.argmax(dim=1).cpu() == target.cpu()).float().mean()) * 100.0    # accuracy in %, :1110
+                    n_batches += 1
+                if n_batches == 0:
+                    raise ValueError("the validation loader is empty")
+                acc_avg = acc_sum / n_batches
+                accuracies[epoch] = acc_avg
+                if acc_avg > max_accuracy:
+                    logging.info("Update accuracy at Epoch {}.".format(epoch))
+                    states = {'noise_estimator': trainer.state_dict(), 'optimizer': {'step': trainer.t, 'lr': trainer.lr}, 'epoch': epoch}
+                    best = os.path.join(args.log_path, "diffu{}_ckpt_best_eph{}_acc{:.4f}.pth".format(mlp_idx, epoch, acc_avg))
+                    torch.save(states, best)
+                    print("Saved diffusion model {} at {}".format(mlp_idx, best))
+                max_accuracy = max(max_accuracy, acc_avg)
+                logging.info(f"epoch: {epoch}, step: {step}, Average diffusion {mlp_idx} accuracy: {acc_avg}%, "
+                             f"Max diffusion {mlp_idx} accuracy: {max_accuracy:.2f}%, ")
+        return {"losses": losses, "accuracies": accuracies, "best": best}
 
     # ---- the hot path (:749-794) --------------------------------------------------------------
     @torch.no_grad()
