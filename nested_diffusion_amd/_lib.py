@@ -261,5 +261,7 @@ def ptr(t) -> int:
 
 
 def current_stream_ptr(device=None) -> Optional[int]:
+    """The raw stream pointer of torch's current stream on `device`: what every entry point takes as its stream.  The package's one
+    lookup -- a wrapper that launched on another stream than the one torch orders its own work on would race silently."""
     import torch
     return torch.cuda.current_stream(device).cuda_stream

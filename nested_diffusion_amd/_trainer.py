@@ -1,5 +1,6 @@
 """What the trainers share (train_mapping.MappingTrainer, train_transformer.ViTTrainer): StepLR, one pass over a loader for training and
-for validation, the reference's epoch loop, and the CLIs' settings."""
+for validation, the reference's epoch loop, and the CLIs' settings.  The third trainer, train_diffusion.NoiseEstimatorTrainer, takes
+nothing from here: it is one training step with its own per-step learning rate (train_diffusion.lr_at), and has no epoch loop to share."""
 from __future__ import annotations
 
 import os

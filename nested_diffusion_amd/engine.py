@@ -63,7 +63,7 @@ class EnsembleEngine:
 
     # -- stream ------------------------------------------------------------------------------
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _lib.current_stream_ptr(self.device)
 
     def _dev(self, t: torch.Tensor) -> torch.Tensor:
         return t.detach().to(device=self.device, dtype=torch.float32).contiguous()

@@ -342,7 +342,7 @@ class GuidingConditioner:
         h = self.handle(B, x.shape[-1])
         n_cls = self.mlps[0].p["linear4.weight"].N
         logits = torch.empty(K, B, n_cls, dtype=torch.float32, device=x.device)
-        check(_lib.load().nd_guiding_prediction(h, ptr(x), ptr(logits), None, B, torch.cuda.current_stream(x.device).cuda_stream),
+        check(_lib.load().nd_guiding_prediction(h, ptr(x), ptr(logits), None, B, _lib.current_stream_ptr(x.device)),
               "nd_guiding_prediction")
         out = list(logits.unbind(0))
         if include_full_vit:

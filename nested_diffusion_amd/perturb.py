@@ -20,7 +20,7 @@ def _img(images: torch.Tensor) -> torch.Tensor:
 
 
 def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+    return _lib.current_stream_ptr(t.device)
 
 
 def add_noise(images_in: torch.Tensor, noise_std: float, z: Optional[torch.Tensor] = None) -> torch.Tensor:

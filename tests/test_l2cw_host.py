@@ -152,7 +152,7 @@ def test_cw_update_hands_over_the_b_of_the_model_space_pass(lo, hi, monkeypatch)
         return 0
 
     monkeypatch.setattr(_lib, "load", lambda: types.SimpleNamespace(nd_cw_update=nd_cw_update))
-    monkeypatch.setattr(ops, "_stream", lambda t: None)
+    monkeypatch.setattr(ops.attack_l2, "_stream", lambda t: None)
     shape = (2, 8)
     s = types.SimpleNamespace(B=2, per=8, **{n: _FakeTensor(shape) for n in ("delta", "m", "v", "x", "t", "best")}, flags=_FakeTensor((2,)))
     ops.cw_update(s, _FakeTensor(shape), _FakeTensor(shape), 0.01, 3, lo, hi)
