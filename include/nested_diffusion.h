@@ -797,6 +797,71 @@ size_t nd_sumsq_workspace_bytes(size_t n);
 int nd_clip_adam(float *w_dev, float *m_dev, float *v_dev, const float *g_dev, size_t n, const float *sumsq_dev, float max_norm,
                  const nd_adam_step *a, void *stream);
 
+/* ---- the input gradient of the ensemble, through the sampler (csrc/nd_ensemble_grad.hip; the chain: ensemble_grad.py SamplerTape and
+ * EnsembleTarget).  The reference has the hook and never uses it: p_sample(..., output_detach=False), diffusion/diffusion_utils.py:80-83,
+ * 103-106, 133-134.  Eval mode, guidance=True, arch 'linear', fp32.  The Linear layers run on nd_linear (scale / shift / softplus epilogue on
+ * the folded tables of nd_load_member: z = a_t[n] (W h)[n] + c_t[n]) and nd_linear_bwd above; these entry points are what the chain has
+ * beyond them.  Rows are r = trial * B + image, M = B * mc.  None of them allocates, copies synchronously, synchronises or uses atomics; every
+ * loop is bounded by the shape arguments; the same bits on every run; all are capturable.  Each listed line is one rounded fp32 operation, no
+ * contraction.
+ *   nd_cond_mul            y[r][n] = s[r][n] * mul[r % B][n] (latent_model.py:177: y = x * y with x = xe [B, N]); s, y [M, N].  The
+ *                          forward's counterpart of the block backward below, a SMALL KERNEL OF ITS OWN, not fused: nd_linear's epilogue
+ *                          gives s1 = softplus(a_t (W1 inp) + c_t), the backward needs s1 itself (d xe = sum d1 s1), lin2 reads y1.
+ *   nd_cond_act_bwd        the eval-mode backward of one ConditionalLinear + BatchNorm1d + softplus block (latent_model.py:101-105, 174-183;
+ *                          also encoder_x.1 / .4 and, with h NULL, norm: latent_model.py:127-135, 155), from the block's taped OUTPUT
+ *                          h = softplus(z) [M, N], one scale row a_t [N] (the folded gain of timestep t) and the optional product operand
+ *                          mul [B, N]:
+ *                              sg = (h > 20) ? 1 : -expm1f(-h)               (= sigma(z); the plain 1 - exp(-h) cancels to 0 for
+ *                                                                              z <~ -16; h NULL: sg = 1, no activation)
+ *                              g = dh * mul[r % B][n]                         (mul NULL: g = dh)
+ *                              du = (g * sg) * a_t[n]
+ *                              acc = acc + (dh * h)                           (mul given; acc = 0, then the image's trials in trial order)
+ *                              dmul_acc[b][n] = dmul_acc[b][n] + acc          (mul given: the block's owner ADDS to what the buffer held,
+ *                                                                              once, after the trials: the T steps accumulate in step order)
+ *                          dh, du [M, N] (du may be dh), dmul_acc [B, N].  M >= 1, B >= 1, M % B == 0, N >= 1 with no alignment demand.
+ *                          One thread owns one column of one image: a_t[n] and mul[b][n] stay in registers across its trials.  A NaN in
+ *                          row r reaches row r of du and its image's dmul_acc only.
+ *   nd_reverse_step        one line of p_sample_loop on the [M, C] state, in the reference's operation order (csrc/nd_step.hpp's
+ *                          nd_posterior / nd_y0_reparam: the device functions the sampler's own kernels use, not a second copy):
+ *                              ND_RSTEP_INIT    out = z + ymean[r % B]                                   (diffusion_utils.py:139-140)
+ *                              ND_RSTEP_UPDATE  out = p_sample's posterior(y, ymean, eps, z; alpha_t, s_t, s_tm1)    (:68-92)
+ *                              ND_RSTEP_LAST    out = 1 / sqrt(1 - s_t^2) * (y - (1 - sqrt(1 - s_t^2)) * ymean - eps * s_t)    (:99-111)
+ *                          y [M, ldy] (its first C columns), eps, z [M, C], ymean [B, C]; alpha_t, s_t = one_minus_alphas_bar_sqrt[t],
+ *                          s_tm1 = its entry t - 1 are the host's table entries.  out [M, ldo]: ldo == C, or 2C <= ldo <= 64, the form
+ *                          lin1 reads: columns C .. 2C-1 = ymean[r % B] (y_0_hat and y_T_mean are one tensor), the rest 0.
+ *   nd_reverse_step_bwd    the backward of one such step.  It is affine in (y_t, y_T_mean, eps): with sab = sqrt(1 - s_t^2) and gamma0..2 of
+ *                          diffusion_utils.py:75-78, cy = gamma0 / sab + gamma1, cm = gamma2 - gamma0 (1 - sab) / sab, ce = -gamma0 s_t / sab;
+ *                          the last step (t = 0): cy = 1 / sab, cm = -(1 - sab) / sab, ce = -s_0 / sab; the start y_T = z + y_T_mean:
+ *                          cm = 1.  The host forms them in double and rounds once (ensemble_grad.reverse_step_coefficients).  g [M, ldg]:
+ *                          columns 0 .. C-1 = dL/dy_{t-1}; ldg >= 2C: columns C .. 2C-1 are the yhat half of the gradient at lin1's input.
+ *                              deps[r][c] = ce * g[r][c]                      (deps [M, C] or NULL)
+ *                              dyadd[r][c] = cy * g[r][c]                     (dyadd [M, lda] or NULL; columns C .. lda-1 are written 0: it
+ *                                                                              is the `add` of lin1's nd_linear_bwd)
+ *                              acc = acc + (cm * g[r][c]);  acc = acc + g[r][C + c] (ldg >= 2C)      (acc = 0; trials in trial order)
+ *                              dymean[b][c] = dymean[b][c] + acc
+ *   nd_aggregate_xent_bwd  the ensemble's own loss (classification_train_separately.py:392-398, 425-447): q_s = softmax(-(y0_s - 1)^2 /
+ *                          temperature), P = (sum_s q_s) / S summed s = 0 .. S-1 with nd_aggregate's operations (P has nd_aggregate's
+ *                          bits), loss[b] = -logf(P[b][y]) formed as -logf(Sy / S), Sy = sum_s q_s[y], and
+ *                              w = q_s[y] / Sy;  t = q_s[c] - [c == y];  dsamples[s][b][c] = (w * t) * ((y0 - 1) * -2 / temperature)
+ *                          samples, dsamples [S, B, C], 1 <= C <= 16.  Conventions as nd_ensemble_xent_bwd: a label outside [0, C):
+ *                          loss NaN, gradient 0, P as usual; a NaN in an image's samples: that image's row of P, its loss and its
+ *                          gradients NaN; P[b][y] == 0: loss +inf, gradient 0.  labels NULL: P only (loss and dsamples may be NULL).
+ *   nd_softmax_bwd         dlogits[r][c] = p[r][c] * (dp[r][c] - dot), dot = sum_c dp[r][c] * p[r][c] in class order; p, dp, dlogits
+ *                          [rows, C] (the conditions yhat [K, B, C] and their gradient).  dlogits is neither input. */
+#define ND_RSTEP_INIT 0
+#define ND_RSTEP_UPDATE 1
+#define ND_RSTEP_LAST 2
+int nd_cond_mul(const float *s_dev, const float *mul_dev, float *y_dev, int M, int N, int B, void *stream);
+int nd_cond_act_bwd(const float *dh_dev, const float *h_dev, const float *a_t_dev, const float *mul_dev, float *du_dev, float *dmul_acc_dev,
+                    int M, int N, int B, void *stream);
+int nd_reverse_step(int mode, const float *y_dev, int ldy, const float *ymean_dev, const float *eps_dev, const float *z_dev, float *out_dev,
+                    int ldo, int M, int B, int C, float alpha_t, float s_t, float s_tm1, void *stream);
+int nd_reverse_step_bwd(const float *g_dev, int ldg, float cy, float cm, float ce, float *deps_dev, float *dyadd_dev, int lda,
+                        float *dymean_dev, int M, int B, int C, void *stream);
+int nd_aggregate_xent_bwd(const float *samples_dev, const int64_t *labels_dev, float *P_dev, float *loss_dev, float *dsamples_dev, int S,
+                          int B, int C, float temperature, void *stream);
+int nd_softmax_bwd(const float *p_dev, const float *dp_dev, float *dlogits_dev, int rows, int C, void *stream);
+
 /* ---- input perturbations of the robustness protocol (diffusion/utils.py:272-414; applied at
  * classification_train_separately.py:726-737).  Images are [B, C, H, W] fp32, contiguous. ------------------- */
 /* add_noise (:272-279): out = x + z * std, z = the randn_like draw (supplied, like the sampler's noise). */

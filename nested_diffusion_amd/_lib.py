@@ -210,6 +210,12 @@ SIGNATURES = {
     "nd_sumsq_plan": (_i, [_sz, C.POINTER(_sz)]),
     "nd_sumsq_workspace_bytes": (_sz, [_sz]),
     "nd_clip_adam": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, C.POINTER(NdAdamStep), _vp]),
+    "nd_cond_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_cond_act_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "nd_reverse_step": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "nd_reverse_step_bwd": (_i, [_vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "nd_aggregate_xent_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "nd_softmax_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -190,8 +190,9 @@ class CarliniWagner:
         if binary_search_steps < 1 or steps < 1:
             raise ValueError("binary_search_steps and steps must be at least 1")
         self.epsilon, self.model = float(epsilon), _vit(model)
+        from .ensemble_grad import EnsembleTarget
         from .mapping import ConditionerTarget
-        if isinstance(self.model, ConditionerTarget):          # refused here, by name, not by an AttributeError in the first iteration
+        if isinstance(self.model, (ConditionerTarget, EnsembleTarget)):   # refused here, by name, not by an AttributeError in the first iteration
             self.model.input_grad_margin()
         self.binary_search_steps, self.steps, self.stepsize = int(binary_search_steps), int(steps), float(stepsize)
         self.confidence, self.initial_const, self.abort_early = float(confidence), float(initial_const), bool(abort_early)

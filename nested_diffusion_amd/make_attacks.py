@@ -1,7 +1,7 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
     python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD --eps E --out ROOT \
-        [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner] [--members 0,1,...]
+        [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner|ensemble] [--members 0,1,...] [--mc N]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
 test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
@@ -13,6 +13,10 @@ Square set: write_attacked_set(config, square.SquareAttack(vit, eps=eps), "SQUAR
 --target conditioner attacks the mapping networks the ensemble is conditioned on instead of the full ViT's head (a white-box attack on the
 defence's front end): the checkpoints are read by mapping.load_conditioner and wrapped in a mapping.ConditionerTarget, whose loss is the
 cross-entropy of the members' averaged softmax; --members selects the members (default: all).
+--target ensemble attacks the ensemble itself, end to end (the adaptive white-box attack): the conditioner and the config's noise-estimator
+checkpoints (diffusion.trained_diffusion_ckpt_path) are wrapped in an ensemble_grad.EnsembleTarget, whose loss is -log of the probability
+test_atk reports, differentiated through the aggregation, the reverse diffusions (--mc trials per member, default 1; batch_size * mc <= 128)
+and both paths from the pixels; every gradient step draws fresh sampler noise.
 """
 from __future__ import annotations
 
@@ -35,9 +39,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--batch_size", type=int, default=32)
     p.add_argument("--dataroot", type=str, default=None)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--target", type=str, choices=["vit", "conditioner"], default="vit",
-                   help="vit: the full ViT's head, as the reference attacks; conditioner: the mapping networks the ensemble is conditioned on")
-    p.add_argument("--members", type=str, default=None, help="--target conditioner: comma-separated member indices (default: all)")
+    p.add_argument("--target", type=str, choices=["vit", "conditioner", "ensemble"], default="vit",
+                   help="vit: the full ViT's head, as the reference attacks; conditioner: the mapping networks the ensemble is conditioned on; "
+                        "ensemble: the whole ensemble, through the sampler")
+    p.add_argument("--members", type=str, default=None, help="--target conditioner / ensemble: comma-separated member indices (default: all)")
+    p.add_argument("--mc", type=int, default=argparse.SUPPRESS, help="--target ensemble: Monte-Carlo trials per member (default 1)")
     return p
 
 
@@ -67,6 +73,18 @@ def load_target(config, device, members=None):
     from .mapping import ConditionerTarget, load_conditioner
 
     return ConditionerTarget(load_conditioner(config.diffusion.trained_aux_cls_ckpt_path, checkpoint_name(config), device), members)
+
+
+def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 0):
+    """--target ensemble: the conditioner and the noise estimators the runner would load for the config's dataset, as the model of a gradient
+    attack on the whole ensemble (ensemble_grad.EnsembleTarget)."""
+    from .ensemble_grad import EnsembleTarget
+    from .mapping import load_checkpoint_object, load_conditioner
+
+    cond = load_conditioner(config.diffusion.trained_aux_cls_ckpt_path, checkpoint_name(config), device)
+    paths = config.diffusion.trained_diffusion_ckpt_path[0]
+    states = [load_checkpoint_object(p)["noise_estimator"] for p in paths[:len(cond.mlps)]]
+    return EnsembleTarget(cond, states, config, mc=mc, members=members, seed=seed)
 
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
@@ -117,12 +135,17 @@ def main(argv=None) -> int:
 
     args = build_parser().parse_args(argv)
     if args.target == "vit" and args.members is not None:
-        raise SystemExit("--members selects members of --target conditioner")
+        raise SystemExit("--members selects members of --target conditioner or ensemble")
+    if args.target != "ensemble" and hasattr(args, "mc"):
+        raise SystemExit("--mc sets the trials of --target ensemble")
     with open(args.config) as f:
         import yaml
         config = nd_main.dict2namespace(yaml.safe_load(f))
     device = torch.device("cuda", args.device)
-    vit = load_vit(config, device) if args.target == "vit" else load_target(config, device, parse_members(args.members))
+    if args.target == "ensemble":
+        vit = load_ensemble_target(config, device, parse_members(args.members), getattr(args, "mc", 1), args.seed)
+    else:
+        vit = load_vit(config, device) if args.target == "vit" else load_target(config, device, parse_members(args.members))
     if args.attack_name == "AUTOPGD":
         attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
     else:

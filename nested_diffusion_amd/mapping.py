@@ -396,6 +396,14 @@ class GuidingConditioner:
         (the logits equal compute_guiding_prediction's bit for bit); the backward is ONE chain down the shared prefix from the deepest
         selected member: each member's dlogits go through its MLP (Classifier.input_grad) and join the running token gradient at its
         level before that level's block gradient.  fp32 (split) form only.  After the optional label check nothing is read back."""
+        logits, tape = self.forward_recorded(x, members)
+        P, loss, dlogits = ops.ensemble_xent_grad(logits, labels, check_labels=check_labels)
+        return P, self.backward(tape, dlogits), loss, logits
+
+    def forward_recorded(self, x: torch.Tensor, members: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, dict]:
+        """The first half of input_grad, for callers that put their own loss at the heads (ensemble_grad.EnsembleTarget): (logits
+        [len(members), B, C] in the order of `members`, tape).  The tape holds what backward needs and is used up by it.  Every refusal of
+        input_grad is made here, before anything is launched."""
         vit = self.vit
         members = self._members(members)
         x = ops._f32(x, "x")
@@ -407,7 +415,7 @@ class GuidingConditioner:
             raise _lib.NdError(f"input_grad: the attention backward takes N <= {ops.ATTENTION_BWD_MAX_TOKENS} tokens per image (N={n_tok})")
         if any(m.p["linear1.weight"].dtype != _lib.ND_DTYPE_F32 for m in self.mlps):
             raise _lib.NdError("input_grad runs in the default fp32 (split) form only: the mapping MLPs hold fp16 images")
-        wT = vit.transposed_weights()                      # refuses fp16 mode and ND_GEMM_F32=mfma_f32
+        vit.transposed_weights()                           # refuses fp16 mode and ND_GEMM_F32=mfma_f32
         top = max(members)
         tok, recs, heads = vit.patch_embed(x), [], {}
         for i in range(top + 1):
@@ -416,17 +424,40 @@ class GuidingConditioner:
             if i in members:
                 heads[i] = self.mlps[i].forward_recorded(tok)
         logits = torch.stack([heads[m][0] for m in members])
-        P, loss, dlogits = ops.ensemble_xent_grad(logits, labels, check_labels=check_labels)
+        return logits, dict(members=members, recs=recs, heads=heads, shape=(B, H, W, n_tok))
+
+    def backward(self, tape: dict, dlogits: torch.Tensor, add: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dx [B, 3, H, W] from dlogits [len(members), B, C] = dL/d(forward_recorded's logits): ONE chain down the shared prefix (input_grad's
+        docstring).  add [B, 3 * H * W]: a gradient that reaches the image by another path (the noise estimators' encoder_x); it joins dx
+        through the image-add kernel (nd_img_add_noise with std = 1: dx + add, one rounding).  The tape's activations are released level by
+        level."""
+        vit = self.vit
+        members, recs, heads = tape["members"], tape["recs"], tape["heads"]
+        B, H, W, n_tok = tape["shape"]
+        dlogits = ops._f32(dlogits, "dlogits")
+        n_cls = self.mlps[0].p["linear4.weight"].N
+        if tuple(dlogits.shape) != (len(members), B, n_cls):
+            raise ValueError(f"dlogits is {tuple(dlogits.shape)}; expected {[len(members), B, n_cls]}")
+        if add is not None:
+            add = ops._f32(add, "add")
+            if tuple(add.shape) != (B, vit.in_chans * H * W) or add.device != dlogits.device:
+                raise ValueError(f"add is {tuple(add.shape)} on {add.device}; expected {[B, vit.in_chans * H * W]} on {dlogits.device}")
+        wT = vit.transposed_weights()
+        top = max(members)
         dtok, dimg = None, None
         for i in range(top, -1, -1):
             if i in heads:
-                add = dtok.reshape(B, -1) if dtok is not None else None
-                dtok = self.mlps[i].input_grad(dlogits[members.index(i)], heads.pop(i)[1], add=add).reshape(B * n_tok, vit.embed_dim)
+                join = dtok.reshape(B, -1) if dtok is not None else None
+                dtok = self.mlps[i].input_grad(dlogits[members.index(i)], heads.pop(i)[1], add=join).reshape(B * n_tok, vit.embed_dim)
                 dimg = ops.split_rows(dtok)
             dtok, dimg = vit._block_grad(i, recs[i], dtok, dimg, B)
             recs[i] = None
         dcols = ops.gemm_split(dimg, wT["patch_embed"])
-        return P, ops.unpatchify(dcols, B, vit.in_chans, H, W, vit.patch), loss, logits
+        dx = ops.unpatchify(dcols, B, vit.in_chans, H, W, vit.patch)
+        if add is None:
+            return dx
+        from .perturb import add_noise
+        return add_noise(dx, 1.0, z=add.reshape(dx.shape))
 
 
 class ConditionerTarget:

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .diffusion_utils import make_beta_schedule
 from .engine import EnsembleEngine
 from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner
@@ -125,13 +125,7 @@ class Diffusion(object):
         cfg = self.config
         mc = mc_trials or self.mc_trials
         if self._states is None:
-            paths = cfg.diffusion.trained_diffusion_ckpt_path[0]
-            states = []
-            for i in range(min(len(paths), self.num_noise_estimators_required)):
-                state = load_checkpoint_object(paths[i])      # {'noise_estimator': state_dict, 'optimizer': ..., 'epoch': ...} (:1120-1126)
-                states.append(state["noise_estimator"])
-                logging.info("Diffusion model %d loaded", i)
-            self._states = states
+            self._states = self._read_noise_estimator_states()
         self.members = [i for i in self.selected_block_indices if i < len(self._states)]
         K = len(self.members)
         self.engine = EnsembleEngine(cfg.data.num_classes, cfg.model.data_dim, cfg.model.hidden_dim, cfg.model.feature_dim,
@@ -143,6 +137,37 @@ class Diffusion(object):
         self._seeded_first = None
         self._seed_noise(0)            # in-library noise (predict_batch without a noise tensor)
         self._states = None            # device copies live in the engine
+
+    def _read_noise_estimator_states(self) -> List[Dict[str, torch.Tensor]]:
+        """:684-697: the 'noise_estimator' state_dicts of the config's checkpoints, in member order."""
+        paths = self.config.diffusion.trained_diffusion_ckpt_path[0]
+        states = []
+        for i in range(min(len(paths), self.num_noise_estimators_required)):
+            state = load_checkpoint_object(paths[i])      # {'noise_estimator': state_dict, 'optimizer': ..., 'epoch': ...} (:1120-1126)
+            states.append(state["noise_estimator"])
+            logging.info("Diffusion model %d loaded", i)
+        return states
+
+    def ensemble_target(self, mc: int = 1, members: Optional[Sequence[int]] = None, seed: Optional[int] = None):
+        """The model of a white-box attack on the ensemble itself (ensemble_grad.EnsembleTarget) from this runner's conditioner, config,
+        temperature and noise-estimator checkpoints: Attack(eps, 'PGD', runner.ensemble_target(mc=2)) is then what test_atk(attack=...)
+        takes.  load_noise_estimators drops the host states once the engine holds them, so this call reads the checkpoints again; states
+        that were injected (no checkpoints on disk) must still be there: build the target before the first test_atk.  The target holds
+        its OWN packed copy of every selected member (the module docstring of ensemble_grad states the bytes)."""
+        from .ensemble_grad import EnsembleTarget
+        if self.operand_dtype != "f32":
+            raise _lib.NdError("ensemble_target runs in the default fp32 form only: not in the fp16 mode")
+        states = self._states
+        if states is None:
+            paths = getattr(self.config.diffusion, "trained_diffusion_ckpt_path", None)
+            if not paths or not paths[0]:
+                raise RuntimeError("the injected noise-estimator states are gone (load_noise_estimators dropped them) and the config names "
+                                   "no checkpoints: call ensemble_target() before load_noise_estimators() / test_atk()")
+            states = self._read_noise_estimator_states()
+        if members is None:
+            members = [i for i in self.selected_block_indices if i < len(states) and i < len(self.cond_pred_model.mlps)]
+        return EnsembleTarget(self.cond_pred_model, states, self.config, mc=mc, members=members, temperature=self.temperature,
+                              seed=self.seed or 0 if seed is None else seed)
 
     def _seed_noise(self, first_image: int) -> None:
         """Seed the library's generator ONCE per (run, shard): nd_seed resets the device-side batch counter, so seeding again before
