@@ -7,6 +7,7 @@ of scope.
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 from typing import List, Optional, Union
 
 import torch
@@ -36,6 +37,22 @@ def make_beta_schedule(schedule="linear", num_timesteps=1000, start=1e-5, end=1e
     if schedule == "cosine_anneal":
         return torch.tensor([start + 0.5 * (end - start) * (1 - math.cos(t / (T - 1) * math.pi)) for t in range(T)])
     raise ValueError(f"unknown beta schedule '{schedule}'")
+
+
+ScheduleTables = namedtuple("ScheduleTables", "betas alphas alphas_bar_sqrt one_minus_alphas_bar_sqrt")
+
+
+def schedule_tables(schedule, num_timesteps, start, end) -> ScheduleTables:
+    """The T-float tables every user of the schedule reads (classification_train_separately.py:215-226): fp32 on the CPU, the reference's
+    torch ops in the reference's order (CPU cumprod), so that every caller holds the same bits -- pinned by tests/golden/schedule.npz.
+    The cosine schedule's 0.9999 goes on one_minus_alphas_bar_sqrt only, as there.  Callers move the tables where they need them."""
+    betas = make_beta_schedule(schedule=schedule, num_timesteps=num_timesteps, start=start, end=end).float()
+    alphas = 1.0 - betas
+    alphas_cumprod = alphas.cumprod(dim=0)
+    one_minus_alphas_bar_sqrt = torch.sqrt(1 - alphas_cumprod)
+    if schedule == "cosine":
+        one_minus_alphas_bar_sqrt = one_minus_alphas_bar_sqrt * 0.9999
+    return ScheduleTables(betas, alphas, torch.sqrt(alphas_cumprod), one_minus_alphas_bar_sqrt)
 
 
 def extract(input, t, x):

@@ -29,17 +29,18 @@ the config's D = 150528, H = F = 4096) plus the folded tables 6 T F 4 bytes per 
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, ops
+from .diffusion_utils import schedule_tables
+from .latent_model import LIN1_K, check_member_dims, member_shapes, pad_lin1
+from .mapping import require_fp32_split
+from .ops import BN_EPS
 from .ops._base import _labels
 
-LIN1_K = 16            # lin1.lin.weight [F, 2C] is held padded to 16 columns, as train_diffusion.LIN1_K: the packed images want K % 16 == 0
 MAX_ROWS = ops.LINEAR_BWD_MAX_M
-BN_EPS = 1e-5
 
 
 # ---- pure host functions (no GPU, no library) ---------------------------------------------------------------------------------------
@@ -78,19 +79,10 @@ def member_dims(state_dict: Dict[str, torch.Tensor]) -> Tuple[int, int, int, int
     F = sh["encoder_x.6.weight"][0]
     C = sh["lin4.weight"][0]
     T = sh["lin1.embed.weight"][0] - 1
-    want = {"encoder_x.0.weight": (H, D), "encoder_x.3.weight": (H, H), "encoder_x.6.weight": (F, H), "lin1.lin.weight": (F, 2 * C),
-            "lin2.lin.weight": (F, F), "lin3.lin.weight": (F, F), "lin4.weight": (C, F), "lin4.bias": (C,)}
-    for name in ("lin1", "lin2", "lin3"):
-        want[name + ".embed.weight"] = (T + 1, F)
-    for k, w in want.items():
+    for k, w in member_shapes(C, D, H, F, T).items():
         if sh[k] != w:
             raise ValueError(f"'{k}' has shape {sh[k]}, expected {w} (guidance=True, arch 'linear')")
-    if min(D, H, F) < 16 or D % 16 or H % 16 or F % 16:
-        raise ValueError(f"data_dim, hidden_dim and feature_dim must be positive multiples of 16 (D={D}, H={H}, F={F})")
-    if not 1 <= 2 * C <= LIN1_K:
-        raise ValueError(f"num_classes must lie in [1, {LIN1_K // 2}] (num_classes={C})")
-    if T < 1:
-        raise ValueError(f"the embedding tables must have T + 1 >= 2 rows (T={T})")
+    check_member_dims(C, D, H, F, T)
     return C, D, H, F, T
 
 
@@ -135,10 +127,8 @@ class SamplerTape:
         self.omabs = one_minus_alphas_bar_sqrt.detach().cpu().float().reshape(-1).tolist()
         self.device = torch.device(device)
         sd = {k: v.detach().to(self.device, torch.float32) for k, v in state_dict.items() if v.is_floating_point()}
-        F, C = self.F, self.C
-        w1 = torch.cat([sd["lin1.lin.weight"], torch.zeros(F, LIN1_K - 2 * C, dtype=torch.float32, device=self.device)], dim=1).contiguous()
         self.w = {"enc0": ops.PackedWeight(sd["encoder_x.0.weight"].contiguous()), "enc3": ops.PackedWeight(sd["encoder_x.3.weight"].contiguous()),
-                  "enc6": ops.PackedWeight(sd["encoder_x.6.weight"].contiguous()), "lin1": ops.PackedWeight(w1),
+                  "enc6": ops.PackedWeight(sd["encoder_x.6.weight"].contiguous()), "lin1": ops.PackedWeight(pad_lin1(sd["lin1.lin.weight"])),
                   "lin2": ops.PackedWeight(sd["lin2.lin.weight"].contiguous()), "lin3": ops.PackedWeight(sd["lin3.lin.weight"].contiguous()),
                   "lin4": ops.PackedWeight(sd["lin4.weight"].contiguous())}
         self.b4 = sd["lin4.bias"].contiguous()
@@ -222,11 +212,8 @@ class SamplerTape:
 # ---- the attacks' model ---------------------------------------------------------------------------------------------------------------
 def check_target_args(conditioner, states, mc: int, members) -> List[int]:
     """Every refusal of EnsembleTarget's constructor, before anything is packed or launched: the selected members."""
-    if getattr(conditioner.vit, "dtype", "f32") != "f32" or any(getattr(m, "p", None) is not None and m.p["linear1.weight"].dtype != _lib.ND_DTYPE_F32
-                                                                for m in conditioner.mlps):
-        raise _lib.NdError("EnsembleTarget runs in the default fp32 form only: not in the fp16 mode")
-    if os.environ.get("ND_GEMM_F32", "b9") == "mfma_f32" or not getattr(conditioner.vit, "split", True):
-        raise _lib.NdError("EnsembleTarget runs in the default fp32 (split) form only: not with ND_GEMM_F32=mfma_f32")
+    require_fp32_split("EnsembleTarget", mlps=conditioner.mlps)              # nothing built here yet: the environment counts
+    require_fp32_split("EnsembleTarget", vit=conditioner.vit)
     if int(mc) < 1:
         raise ValueError(f"mc must be at least 1 (mc={mc})")
     members = conditioner._members(members if members is not None else range(min(len(states), len(conditioner.mlps))))
@@ -260,21 +247,15 @@ class EnsembleTarget:
         self.temperature = float(temperature)
         if not self.temperature > 0.0:
             raise ValueError(f"temperature must be > 0 (temperature={temperature})")
-        from .diffusion_utils import make_beta_schedule
         self.T = int(config.diffusion.timesteps)
-        betas = make_beta_schedule(schedule=config.diffusion.beta_schedule, num_timesteps=self.T, start=config.diffusion.beta_start,
-                                   end=config.diffusion.beta_end).float()                # classification_train_separately.py:215-226
-        alphas = 1.0 - betas
-        omabs = torch.sqrt(1 - alphas.cumprod(dim=0))
-        if config.diffusion.beta_schedule == "cosine":
-            omabs = omabs * 0.9999
+        tables = schedule_tables(config.diffusion.beta_schedule, self.T, config.diffusion.beta_start, config.diffusion.beta_end)
         dims = [member_dims(states[k]) for k in self.members]
         want = (int(config.data.num_classes), int(config.model.data_dim), int(config.model.hidden_dim), int(config.model.feature_dim))
         for k, d in zip(self.members, dims):
             if d[:4] != want or d[4] < self.T:
                 raise ValueError(f"member {k} has (C, D, H, F, T) = {d}; the config says {want} and {self.T} timesteps")
         self.C, self.D = want[0], want[1]
-        self.tapes = [SamplerTape(states[k], alphas, omabs, self.device) for k in self.members]
+        self.tapes = [SamplerTape(states[k], tables.alphas, tables.one_minus_alphas_bar_sqrt, self.device) for k in self.members]
         self._calls = 0
         self._fixed: Optional[torch.Tensor] = None
 

@@ -10,13 +10,46 @@ LeNet5; latent_model.py:50-90, 216-368) are never instantiated by the shipped co
 from __future__ import annotations
 
 import weakref
-from typing import Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .engine import EnsembleEngine
+
+
+# ---- the layout of ConditionalModel(guidance=True, arch 'linear'), for everything that holds one without the nn.Module -----------------
+LIN1_K = 16     # lin1.lin.weight [F, 2C] is held padded to 16 columns wherever it is a packed image: those want K % 16 == 0
+
+
+def member_shapes(C: int, D: int, H: int, F: int, T: int) -> Dict[str, Tuple[int, ...]]:
+    """The reference's parameter shapes (latent_model.py:108-167; embedding tables of T + 1 rows), in registration order."""
+    s: Dict[str, Tuple[int, ...]] = {}
+    for name, n_in, n_out, after in (("encoder_x.0", D, H, "encoder_x.1"), ("encoder_x.3", H, H, "encoder_x.4"), ("encoder_x.6", H, F, "norm"),
+                                     ("lin1.lin", 2 * C, F, "unetnorm1"), ("lin2.lin", F, F, "unetnorm2"), ("lin3.lin", F, F, "unetnorm3"),
+                                     ("lin4", F, C, None)):
+        s[name + ".weight"], s[name + ".bias"] = (n_out, n_in), (n_out,)             # a Linear
+        if name.endswith(".lin"):
+            s[name[:-4] + ".embed.weight"] = (T + 1, F)                               # ConditionalLinear's per-timestep gain
+        if after:
+            s[after + ".weight"] = s[after + ".bias"] = (n_out,)                      # the BatchNorm1d behind it
+    return s
+
+
+def check_member_dims(C: int, D: int, H: int, F: int, T: int) -> None:
+    """What the packed images and the kernels behind them take: D, H, F positive multiples of 16, 1 <= 2C <= LIN1_K, T >= 1."""
+    if min(D, H, F) < 16 or D % 16 or H % 16 or F % 16:
+        raise ValueError(f"data_dim, hidden_dim and feature_dim must be positive multiples of 16 (D={D}, H={H}, F={F})")
+    if not 1 <= 2 * C <= LIN1_K:
+        raise ValueError(f"num_classes must lie in [1, {LIN1_K // 2}] (num_classes={C})")
+    if T < 1:
+        raise ValueError(f"diffusion.timesteps must be at least 1: the embedding tables must have T + 1 >= 2 rows (T={T})")
+
+
+def pad_lin1(w: torch.Tensor) -> torch.Tensor:
+    """lin1.lin.weight [F, 2C] -> [F, LIN1_K]: the input first, the new columns +0.0 (the trainer's gradient there is exactly +0)."""
+    return torch.cat([w, torch.zeros(w.shape[0], LIN1_K - w.shape[1], dtype=w.dtype, device=w.device)], dim=1).contiguous()
 
 
 class _TensorKey:

@@ -15,10 +15,10 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import _lib, ops
-from .diffusion_utils import make_beta_schedule
+from . import ops
+from .diffusion_utils import schedule_tables
 from .engine import EnsembleEngine
-from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner
+from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner, require_fp32_split
 from . import dist as nd_dist
 
 CHEST = ['ChestXRay', 'ChestXRayAtkFGSM', 'ChestXRayAtkPGD', 'ChestXRayAtkBIM', 'ChestXRayAtkAUTOPGD', 'ChestXRayAtkCW',
@@ -71,17 +71,9 @@ class Diffusion(object):
         self.device = torch.device(device)
         self.num_timesteps = config.diffusion.timesteps
         self.mc_trials = int(getattr(args, "mc_trials", 20) or 20)          # hard-coded 20 at :770
-        # schedule (:215-226): same torch ops as the reference, fp32
-        betas = make_beta_schedule(schedule=config.diffusion.beta_schedule, num_timesteps=self.num_timesteps,
-                                   start=config.diffusion.beta_start, end=config.diffusion.beta_end)
-        betas = betas.float()                                    # T-float init tables: host ops in the reference's
-        alphas = 1.0 - betas                                     # order (CPU cumprod), pinned by tests/golden/schedule.npz
-        omabs = torch.sqrt(1 - alphas.cumprod(dim=0))
-        if config.diffusion.beta_schedule == "cosine":
-            omabs = omabs * 0.9999
-        self.betas = betas.to(self.device)
-        self.alphas = alphas.to(self.device)
-        self.one_minus_alphas_bar_sqrt = omabs.to(self.device)
+        tables = schedule_tables(config.diffusion.beta_schedule, self.num_timesteps, config.diffusion.beta_start, config.diffusion.beta_end)
+        self.betas, self.alphas = tables.betas.to(self.device), tables.alphas.to(self.device)
+        self.one_minus_alphas_bar_sqrt = tables.one_minus_alphas_bar_sqrt.to(self.device)
         self.temperature = temperature_for(config.data.dataset)
         self.selected_block_indices = [0, 1, 2, 3, 4]                       # :275
         if conditioner is None:
@@ -155,8 +147,7 @@ class Diffusion(object):
         that were injected (no checkpoints on disk) must still be there: build the target before the first test_atk.  The target holds
         its OWN packed copy of every selected member (the module docstring of ensemble_grad states the bytes)."""
         from .ensemble_grad import EnsembleTarget
-        if self.operand_dtype != "f32":
-            raise _lib.NdError("ensemble_target runs in the default fp32 form only: not in the fp16 mode")
+        require_fp32_split("ensemble_target", dtype=self.operand_dtype)
         states = self._states
         if states is None:
             paths = getattr(self.config.diffusion, "trained_diffusion_ckpt_path", None)

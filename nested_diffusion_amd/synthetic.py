@@ -53,11 +53,10 @@ def make_denoiser(p: Dict[str, torch.Tensor], y_dim: int, n_steps: int, gain: fl
     per-timestep gain 1/sqrt(1 - abar_t) in its embedding rows (latent_model.py:101-105), lin2 / lin3 / lin4 take pair
     differences -- exactly linear since softplus(p) - softplus(-p) = p -- and xe is 1 on those features.  All other features
     stay random.  Same construction as the oracle's initialiser that golden fixture `sampler_s4` was generated with."""
-    from .diffusion_utils import make_beta_schedule
+    from .diffusion_utils import schedule_tables
     C, S = y_dim, 2 * y_dim
     dev = p["lin4.weight"].device
-    betas = make_beta_schedule(schedule="linear", num_timesteps=n_steps, start=beta_start, end=beta_end).float()
-    omabs = torch.sqrt(1 - (1.0 - betas).cumprod(dim=0)).to(dev)
+    omabs = schedule_tables("linear", n_steps, beta_start, beta_end).one_minus_alphas_bar_sqrt.to(dev)
 
     def bn_identity(name, shift=0.0):
         p[name + ".weight"][:S] = 1.0

@@ -22,9 +22,9 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib, _trainer, ops
+from . import _trainer, ops
 from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
-from .mapping import LN_EPS, VisionTransformer, load_pickled
+from .mapping import LN_EPS, VisionTransformer, load_pickled, require_fp32_split
 from .train_mapping import TRAIN_DIR, VALID_DIR, make_loaders
 
 # mapping/train_transformer.py:47-49, 95-97 (the two datasets this package has a loader for)
@@ -94,10 +94,7 @@ class ViTTrainer(EpochTrainer):
 
     def __init__(self, state_dict: Optional[Dict[str, torch.Tensor]], num_classes: int = 2, num_heads: int = 12, lr: float = 1e-4,
                  weight_decay: float = 0.1, step_size: int = 10, gamma: float = 0.5, seed: int = 0, device="cuda", dtype="f32", **arch):
-        if _lib.dtype_code(dtype) != _lib.ND_DTYPE_F32:
-            raise _lib.NdError("ViTTrainer runs in the default fp32 (split) form only: not in fp16 mode (dtype='f16')")
-        if os.environ.get("ND_GEMM_F32", "b9") == "mfma_f32":
-            raise _lib.NdError("ViTTrainer runs in the default fp32 (split) form only: not with ND_GEMM_F32=mfma_f32")
+        require_fp32_split("ViTTrainer", dtype=dtype)                   # before anything is built
         if state_dict is None:
             sd = init_state_dict(num_classes, seed=seed, **arch)
         else:
@@ -107,9 +104,7 @@ class ViTTrainer(EpochTrainer):
             if sd["head.weight"].shape[0] != num_classes:
                 sd.update(_fresh_head(num_classes, sd["head.weight"].shape[1], torch.Generator().manual_seed(int(seed))))
         self.vit = VisionTransformer(sd, num_heads, device)
-        if not self.vit.split:
-            raise _lib.NdError("ViTTrainer runs in the default fp32 (split) form only: every GEMM depth must be a multiple of 32 "
-                               "(not fp16 mode, not ND_GEMM_F32=mfma_f32)")
+        require_fp32_split("ViTTrainer", vit=self.vit)
         self.device = self.vit.device
         self.base_lr, self.weight_decay, self.step_size, self.gamma = float(lr), float(weight_decay), int(step_size), float(gamma)
         self.epoch, self.t = 0, 0                               # scheduler steps taken, AdamW steps taken

@@ -153,6 +153,29 @@ def test_schedule_and_temperature_match_pinned_tables():
         temperature_for("MNIST")
 
 
+def test_schedule_tables_match_pinned_tables_and_the_oracle():
+    """The one function the runner, the ensemble target, the trainer and the synthetic denoiser take their tables from."""
+    import numpy as np
+    from nested_diffusion_amd.diffusion_utils import schedule_tables
+    from oracle import ref_cpu
+    z = np.load(os.path.join(ROOT, "tests", "golden", "schedule.npz"))
+    for T in (10, 100, 1000):
+        tables = schedule_tables("linear", T, 1e-4, 0.02)
+        betas, alphas, alphas_bar_sqrt, omabs = tables
+        assert all(t.dtype == torch.float32 and t.device.type == "cpu" and tuple(t.shape) == (T,) for t in tables)
+        assert np.array_equal(betas.numpy(), z[f"betas_{T}"])
+        assert np.array_equal(alphas.numpy(), z[f"alphas_{T}"])
+        assert np.array_equal(omabs.numpy(), z[f"omabs_{T}"])
+        assert omabs is tables.one_minus_alphas_bar_sqrt and alphas_bar_sqrt is tables.alphas_bar_sqrt
+        assert torch.equal(alphas_bar_sqrt, torch.sqrt((1 - betas).cumprod(0)))
+    got = schedule_tables("cosine", 50, 1e-4, 0.02)                        # the 0.9999 factor, on one_minus_alphas_bar_sqrt only
+    want_alphas, want_omabs = ref_cpu.schedule_tables("cosine", 50, 1e-4, 0.02)
+    assert torch.equal(got.alphas, want_alphas) and torch.equal(got.one_minus_alphas_bar_sqrt, want_omabs)
+    assert np.array_equal(got.betas.numpy(), z["betas_cosine_50"])
+    assert torch.equal(got.alphas_bar_sqrt, torch.sqrt((1 - got.betas).cumprod(0)))
+    assert not torch.equal(got.one_minus_alphas_bar_sqrt, torch.sqrt(1 - (1 - got.betas).cumprod(0)))
+
+
 def test_shard_bounds_cover_and_balance():
     from nested_diffusion_amd.dist import shard_bounds
     for n in (0, 1, 7, 32, 70, 256):

@@ -155,6 +155,36 @@ def test_ensemble_target_refuses_bad_arguments_without_a_gpu(monkeypatch):
         member_dims({k: v for k, v in states[0].items() if k != "norm.weight"})
 
 
+def test_member_layout_is_the_reference_models():
+    """latent_model's layout of the noise estimator -- what the trainer and the ensemble gradient both hold their members by -- against
+    the module it describes, built on the CPU."""
+    import struct
+    from nested_diffusion_amd import ensemble_grad, latent_model, ops, train_diffusion
+    C, D, H, F, T = 2, 32, 16, 16, 3
+    ns = types.SimpleNamespace
+    config = ns(data=ns(dataset="ChestXRay", num_classes=C), model=ns(data_dim=D, hidden_dim=H, feature_dim=F, arch="linear"),
+                diffusion=ns(timesteps=T))
+    model = latent_model.ConditionalModel(config, guidance=True)
+    params = {k: tuple(p.shape) for k, p in model.named_parameters()}
+    table = latent_model.member_shapes(C, D, H, F, T)
+    assert table == params and list(table) == list(params) == list(train_diffusion.PARAM_KEYS)     # key for key, in registration order
+    assert latent_model.LIN1_K == 16 and train_diffusion.LIN1_K is latent_model.LIN1_K and ensemble_grad.LIN1_K is latent_model.LIN1_K
+    assert ensemble_grad.BN_EPS == ops.BN_EPS == model.norm.eps
+    latent_model.check_member_dims(C, D, H, F, T)
+    with pytest.raises(ValueError, match="multiples of 16"):
+        latent_model.check_member_dims(C, 24, H, F, T)
+    with pytest.raises(ValueError, match="num_classes"):
+        latent_model.check_member_dims(9, D, H, F, T)
+    with pytest.raises(ValueError, match="T=0"):
+        latent_model.check_member_dims(C, D, H, F, 0)
+    w = torch.randn(F, 2 * C, generator=torch.Generator().manual_seed(1))
+    w[0, 0] = -0.0
+    padded = latent_model.pad_lin1(w)
+    assert tuple(padded.shape) == (F, 16) and padded.dtype == torch.float32 and padded.is_contiguous()
+    assert padded[:, :2 * C].contiguous().numpy().tobytes() == w.numpy().tobytes()
+    assert padded[:, 2 * C:].contiguous().numpy().tobytes() == struct.pack("<f", 0.0) * (F * (16 - 2 * C))      # +0.0, bit for bit
+
+
 def test_ensemble_target_is_not_unwrapped_and_cw_refuses_by_name():
     from nested_diffusion_amd import attack
     from nested_diffusion_amd.ensemble_grad import EnsembleTarget
