@@ -879,6 +879,14 @@ int nd_img_resize_bilinear(const float *x_dev, float *out_dev, int B, int C, int
 /* random_cover_new (:315-349): zero n_rects squares of side `side` per image, in place; rects_dev [B][n_rects][2]
  * int32 = (top, left), chosen on the host with the reference's rejection sampling. */
 int nd_img_cover(float *x_dev, int B, int C, int H, int W, const int32_t *rects_dev, int n_rects, int side, void *stream);
+/* The training input (replaces ImageFolderDataset.__getitem__ + the DataLoader's collate for a device-resident set): one batch
+ * out [B][3][pixels] fp32 from the decoded uint8 store [n_images][src_channels][pixels] (src_channels 1: the three planes are equal
+ * and stored once; 3: RGB planes): out[b][c][p] = lut[c][store[idx[b]][src_channels == 1 ? 0 : c][p]].  lut_dev [3][256] fp32 is
+ * ToTensor's /255 (and Normalize) of every byte value, made on the host with the dataset's own expressions: the kernel does no
+ * arithmetic on values.  idx_dev: int32 [B]; a row whose index is outside [0, n_images) reads nothing and writes nothing.
+ * out / lut / idx 4-byte aligned; offsets into the store are 64-bit (n_images * src_channels * pixels may pass 2^31). */
+int nd_img_gather_u8(const uint8_t *store_dev, long long n_images, int src_channels, int pixels, const int32_t *idx_dev, int B,
+                     const float *lut_dev, float *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,7 @@ SIGNATURES = {
     "nd_img_contrast": (_i, [_vp, _vp, _vp, _i, _sz, _f, _vp]),
     "nd_img_resize_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "nd_img_cover": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "nd_img_gather_u8": (_i, [_vp, C.c_longlong, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "nd_layernorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "nd_gelu_split": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "nd_gelu_bwd_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),

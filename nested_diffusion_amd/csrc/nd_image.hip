@@ -1,6 +1,6 @@
 // nd_image.hip -- input-side perturbations of the robustness protocol (diffusion/utils.py:272-414, applied at
-// classification_train_separately.py:726-737).  Elementwise / resampling kernels on [B, C, H, W] fp32 images.
-// gfx950 only.
+// classification_train_separately.py:726-737): elementwise / resampling kernels on [B, C, H, W] fp32 images; and the batch
+// gather of the training input (a device-resident uint8 image store -> one fp32 batch).  gfx950 only.
 #include "nd_host.hpp"
 
 static inline dim3 grid1(size_t n, int per = 256) {
@@ -79,6 +79,44 @@ __global__ void k_cover(float* __restrict__ x, int B, int C, int H, int W, const
     }
 }
 
+// Training input: out[b][c][p] = lut[c][store[idx[b]][Cs == 1 ? 0 : c][p]] -- one batch formed from the device-resident uint8 store.
+// The byte -> float transform is the 3 x 256 table (staged in LDS once per workgroup), so no arithmetic touches a value.  Workgroups
+// (x, y) walk whole image rows: y the batch rows, x the pixels of one.  VEC: a lane loads 4 bytes per channel and stores one float4
+// (pixels % 4 == 0 and 4- / 16-byte aligned bases, decided by the host); otherwise a byte and a float.  Offsets into the store are 64-bit.
+// A row whose index is outside [0, n_images) reads nothing and writes nothing (the index lives on the device: the host cannot refuse it).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gather_u8(const uint8_t* __restrict__ store, long long n_images, int Cs, int pixels,
+                                                   const int* __restrict__ idx, int B, const float* __restrict__ lut, float* __restrict__ out) {
+    __shared__ float t[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += 256) t[i] = lut[i];
+    __syncthreads();
+    const size_t cstride = Cs == 1 ? 0 : (size_t)pixels;
+    const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const long long r = idx[b];
+        if (r < 0 || r >= n_images) continue;
+        const uint8_t* src = store + (size_t)r * (size_t)Cs * (size_t)pixels;
+        float* dst = out + (size_t)b * 3 * (size_t)pixels;
+        if (VEC) {
+            const size_t quads = (size_t)pixels >> 2;
+            for (size_t q = first; q < quads; q += step) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c == 0 || Cs == 3) w = reinterpret_cast<const uint32_t*>(src + c * cstride)[q];
+                    const float* tc = t + c * 256;
+                    reinterpret_cast<float4*>(dst + (size_t)c * pixels)[q] =
+                        make_float4(tc[w & 255u], tc[(w >> 8) & 255u], tc[(w >> 16) & 255u], tc[w >> 24]);
+                }
+            }
+        } else {
+            for (size_t p = first; p < (size_t)pixels; p += step)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dst[(size_t)c * pixels + p] = t[c * 256 + src[c * cstride + p]];
+        }
+    }
+}
+
 extern "C" int nd_img_add_noise(const float* x, const float* z, float* out, size_t n, float std_, void* stream) {
     if (!x || !z || !out || n == 0) return nd_set_err(ND_ERR_ARG, "bad add_noise arguments");
     hipLaunchKernelGGL(k_add_noise, grid1(n), dim3(256), 0, (hipStream_t)stream, x, z, out, n, std_);
@@ -121,6 +159,25 @@ extern "C" int nd_img_cover(float* x, int B, int C, int H, int W, const int32_t*
     if (side == 0) return ND_OK;
     const size_t total = (size_t)B * n_rects * C * side * side;
     hipLaunchKernelGGL(k_cover, grid1(total), dim3(256), 0, (hipStream_t)stream, x, B, C, H, W, (const int*)rects, n_rects, side);
+    HIP_CHECK(hipGetLastError());
+    return ND_OK;
+}
+extern "C" int nd_img_gather_u8(const uint8_t* store, long long n_images, int src_channels, int pixels, const int32_t* idx, int B,
+                                const float* lut, float* out, void* stream) {
+    if (!store || !idx || !lut || !out) return nd_set_err(ND_ERR_ARG, "gather_u8: NULL tensor");
+    if (src_channels != 1 && src_channels != 3) return nd_set_err(ND_ERR_ARG, "gather_u8 needs src_channels 1 or 3 (src_channels=%d)", src_channels);
+    if (pixels < 1 || B < 1 || n_images < 1)
+        return nd_set_err(ND_ERR_ARG, "gather_u8 needs pixels, B, n_images >= 1 (pixels=%d, B=%d, n_images=%lld)", pixels, B, n_images);
+    if (((uintptr_t)out | (uintptr_t)lut | (uintptr_t)idx) & 3)
+        return nd_set_err(ND_ERR_ARG, "gather_u8: out, lut and idx must be 4-byte aligned");
+    const bool vec = pixels % 4 == 0 && ((uintptr_t)store & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    const size_t per_wg = vec ? 2048 : 512;                          // pixels of a row per workgroup: two passes of its 256 lanes
+    const size_t gx = ((size_t)pixels + per_wg - 1) / per_wg;
+    const dim3 grid((unsigned)(gx > 65535 ? 65535 : gx), (unsigned)(B > 65535 ? 65535 : B));
+    if (vec)
+        hipLaunchKernelGGL(k_gather_u8<true>, grid, dim3(256), 0, (hipStream_t)stream, store, n_images, src_channels, pixels, (const int*)idx, B, lut, out);
+    else
+        hipLaunchKernelGGL(k_gather_u8<false>, grid, dim3(256), 0, (hipStream_t)stream, store, n_images, src_channels, pixels, (const int*)idx, B, lut, out);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

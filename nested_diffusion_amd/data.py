@@ -1,6 +1,7 @@
-"""Test-set loaders: the reference's disk layout (ImageFolder + Grayscale/Resize/ToTensor,
-dataset_helper/chest_x_ray_dataset.py; host-side decode with PIL, as torchvision does) and a synthetic loader
-of the same tensor contract: batches (images [B,3,224,224] float32, target [B] int64)."""
+"""Loaders: the reference's disk layout (ImageFolder + Grayscale/Resize/ToTensor,
+dataset_helper/chest_x_ray_dataset.py; host-side decode with PIL, as torchvision does), a synthetic loader
+of the same tensor contract: batches (images [B,3,224,224] float32, target [B] int64), and the training side's device-resident
+set (DeviceImageSet: decoded once, held on the GPU as bytes, batches gathered by one HIP launch in the DataLoader's order)."""
 from __future__ import annotations
 
 import os
@@ -78,14 +79,16 @@ class ImageFolderDataset(torch.utils.data.Dataset):
                 for f in sorted(files):
                     if f.lower().endswith(IMG_EXTENSIONS):
                         self.samples.append((os.path.join(d, f), self.class_to_idx[c]))
-        self.preprocess, self.size = preprocess, tuple(image_size)
+        self.root, self.preprocess, self.size = root, preprocess, tuple(image_size)
         if preprocess != "attacked":
             self.mean, self.std = (torch.tensor(v).view(3, 1, 1) for v in PRECAL[dataset_name])
 
     def __len__(self):
         return len(self.samples)
 
-    def __getitem__(self, i):
+    def load_u8(self, i):
+        """(uint8 ndarray [3, H, W], target): sample i decoded, converted and resized -- everything of __getitem__ before ToTensor.  With
+        byte_table() this is the whole per-sample state (none of the reference's training transforms is random)."""
         import numpy as np
         from PIL import Image
         path, target = self.samples[i]
@@ -95,10 +98,216 @@ class ImageFolderDataset(torch.utils.data.Dataset):
             g = np.array(img.convert("L"), dtype=np.uint8)                      # F.to_grayscale(img, 3)
             img = Image.fromarray(np.dstack([g, g, g]), "RGB")
         img = img.resize(self.size[::-1], Image.BILINEAR)                       # Resize((h, w)) on a PIL image
-        x = torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).contiguous().float().div(255)   # ToTensor
+        return np.ascontiguousarray(np.array(img, dtype=np.uint8).transpose(2, 0, 1)), target
+
+    def _to_float(self, x: torch.Tensor) -> torch.Tensor:
+        """ToTensor's /255 and, for standardized, Normalize, on a uint8 tensor [3, ...] with two trailing axes."""
+        x = x.float().div(255)                                                  # ToTensor
         if self.preprocess == "standardized":
             x = (x - self.mean) / self.std                                      # Normalize
-        return x, target
+        return x
+
+    def byte_table(self) -> torch.Tensor:
+        """float32 [3, 256]: what __getitem__ makes of byte value v in channel c, by the same tensor expressions (each is one correctly
+        rounded operation per element, so a table entry has the bits of the pixel)."""
+        return self._to_float(torch.arange(256, dtype=torch.uint8).view(1, 256, 1).repeat(3, 1, 1)).view(3, 256).contiguous()
+
+    def __getitem__(self, i):
+        a, target = self.load_u8(i)
+        return self._to_float(torch.from_numpy(a)), target
+
+
+# ---- device-resident training sets: decode once, keep the bytes on the GPU, gather every batch with one launch (nd_img_gather_u8) ------
+STORE_FORMAT = 1
+MAX_WORKERS = 16                  # a command on the GPU machines may use 16 CPUs; os.cpu_count() shows the whole machine's
+UPLOAD_CHUNK = 64 << 20           # bytes per host -> device copy of the store
+CACHE_CHOICES = ("none", "device")   # the trainers' --cache / --train_cache
+
+
+def cache_file(cache_dir, split: str, ds):
+    """<cache_dir>/<split>_<preprocess>_<H>x<W>.npz, or None without a cache_dir."""
+    return os.path.join(cache_dir, f"{split}_{ds.preprocess}_{ds.size[0]}x{ds.size[1]}.npz") if cache_dir else None
+
+
+def _workers(workers) -> int:
+    if workers is None:
+        return min(MAX_WORKERS, len(os.sched_getaffinity(0)))
+    workers = int(workers)
+    if not 1 <= workers <= MAX_WORKERS:
+        raise ValueError(f"workers must be in [1, {MAX_WORKERS}] (workers={workers})")
+    return workers
+
+
+def build_store(dataset, workers=None):
+    """(store uint8 ndarray [N, Cs, H, W], targets int64 ndarray [N]): every sample's load_u8, decoded by a pool of `workers` threads
+    (Pillow releases the GIL in decode, convert and resize).  Cs = 1 when the three planes of EVERY image are equal (checked here, image
+    by image; always so for 'grayscaled'), else 3."""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    workers, n = _workers(workers), len(dataset)
+    if n < 1:
+        raise ValueError("build_store: the dataset is empty")
+    H, W = dataset.size
+    store = np.empty((n, 3, H, W), dtype=np.uint8)
+    targets = np.empty(n, dtype=np.int64)
+
+    def one(i):
+        a, targets[i] = dataset.load_u8(i)
+        store[i] = a
+        return bool((a[0] == a[1]).all() and (a[0] == a[2]).all())
+
+    if workers == 1:
+        gray = [one(i) for i in range(n)]
+    else:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            gray = list(pool.map(one, range(n)))
+    return (np.ascontiguousarray(store[:, :1]) if all(gray) else store), targets
+
+
+def store_manifest(dataset) -> dict:
+    """What a cached store depends on, read from the directory as it is now: format version, preprocess, image size, Pillow's version and
+    per sample (relative path, file size, mtime_ns, target).  The normalisation constants are not in it: the bytes do not depend on them."""
+    import PIL
+    samples = []
+    for path, target in dataset.samples:
+        st = os.stat(path)
+        samples.append([os.path.relpath(path, dataset.root), st.st_size, st.st_mtime_ns, int(target)])
+    return {"format": STORE_FORMAT, "preprocess": dataset.preprocess, "size": list(dataset.size), "pillow": PIL.__version__, "samples": samples}
+
+
+def _read_store(cache_path: str, manifest: dict):
+    """(store, targets) of a cache file whose manifest equals `manifest`, else None (also for a truncated or unreadable file)."""
+    import json
+    import numpy as np
+    try:
+        with np.load(cache_path, allow_pickle=False) as z:
+            saved = json.loads(bytes(z["manifest"]).decode("utf-8"))
+            channels = saved.pop("channels")
+            if saved != manifest:
+                return None
+            store, targets = z["store"], z["targets"]
+    except Exception:                                       # missing, truncated, not a zip, a missing member, not JSON: rebuild
+        return None
+    n = len(manifest["samples"])
+    if store.dtype != np.uint8 or store.shape != (n, channels, *manifest["size"]) or channels not in (1, 3):
+        return None
+    if targets.dtype != np.int64 or targets.shape != (n,) or targets.tolist() != [s[3] for s in manifest["samples"]]:
+        return None
+    return store, targets
+
+
+def load_or_build_store(dataset, cache_path: str, workers=None):
+    """build_store through one uncompressed .npz (store, targets, manifest; read with allow_pickle=False): reused when its manifest equals
+    store_manifest(dataset), otherwise rebuilt and replaced atomically (a temporary file in the same directory, then os.replace)."""
+    import json
+    import tempfile
+    import numpy as np
+    manifest = store_manifest(dataset)
+    got = _read_store(cache_path, manifest)
+    if got is not None:
+        return got
+    store, targets = build_store(dataset, workers)
+    blob = json.dumps(dict(manifest, channels=int(store.shape[1]))).encode("utf-8")
+    d = os.path.dirname(os.path.abspath(cache_path))
+    os.makedirs(d, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(dir=d, prefix=os.path.basename(cache_path) + ".", suffix=".tmp")
+    try:
+        with os.fdopen(fd, "wb") as f:
+            np.savez(f, store=store, targets=targets, manifest=np.frombuffer(blob, dtype=np.uint8))
+        os.replace(tmp, cache_path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    return store, targets
+
+
+def check_indices(idx, n: int) -> torch.Tensor:
+    """The indices of one batch request as a CPU int64 tensor [B >= 1], every one in [0, n); anything else is refused here, on the host,
+    before an index reaches the device."""
+    idx = torch.as_tensor(idx)
+    if idx.is_cuda:
+        raise ValueError("batch indices must be on the CPU (they come from a CPU sampler and are range-checked before the upload)")
+    if idx.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise TypeError(f"batch indices must be integers (dtype={idx.dtype})")
+    if idx.dim() != 1:
+        raise ValueError(f"batch indices must be one-dimensional (shape={tuple(idx.shape)})")
+    if idx.numel() < 1:
+        raise ValueError("a batch needs at least one index")
+    idx = idx.to(torch.int64).contiguous()
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= n:
+        raise IndexError(f"batch indices must lie in [0, {n}) (min={lo}, max={hi})")
+    return idx
+
+
+def _free_device_bytes(device) -> int:
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+class IndexBatchLoader:
+    """An iterable with __len__ over image_set.batch(idx): the index batches come from a real torch.utils.data.DataLoader over an
+    index-only dataset with the same arguments, so the order -- and every draw from the generator (or the global one) -- is that of
+    DataLoader(dataset, batch_size, shuffle, generator=generator, drop_last=drop_last), with no restatement of torch's samplers."""
+
+    def __init__(self, image_set, batch_size: int, shuffle: bool = False, generator=None, drop_last: bool = False):
+        self.image_set = image_set
+        self.indices = torch.utils.data.DataLoader(range(len(image_set)), batch_size=batch_size, shuffle=shuffle, generator=generator,
+                                                   drop_last=drop_last)
+
+    def __len__(self):
+        return len(self.indices)
+
+    def __iter__(self):
+        for idx in self.indices:
+            yield self.image_set.batch(idx)
+
+
+class DeviceImageSet:
+    """An ImageFolderDataset decoded once and held on the GPU as bytes: store uint8 [N, Cs, H, W] (device), targets int64 [N] (CPU), lut
+    float32 [3, 256] (device; dataset.byte_table()).  batch(idx) forms a batch with one nd_img_gather_u8 launch, bit for bit the tensors
+    DataLoader(dataset) collates.  cache_path: the decoded store is kept in / reused from that file (load_or_build_store).  max_bytes
+    (default: half of the free device memory now): a larger store is refused before anything is decoded."""
+
+    def __init__(self, dataset, device="cuda", workers=None, cache_path=None, max_bytes=None):
+        n, (H, W) = len(dataset), dataset.size
+        if n < 1:
+            raise ValueError("DeviceImageSet: the dataset is empty")
+        self.device = torch.device(device)
+        if max_bytes is None:
+            max_bytes = _free_device_bytes(self.device) // 2
+        self._refuse_above(n * (1 if dataset.preprocess == "grayscaled" else 3) * H * W, int(max_bytes))
+        store, targets = load_or_build_store(dataset, cache_path, workers) if cache_path else build_store(dataset, workers)
+        self._refuse_above(store.nbytes, int(max_bytes))
+        self.size, self.targets = (H, W), torch.from_numpy(targets)
+        self.store = torch.empty(store.shape, dtype=torch.uint8, device=self.device)
+        rows = max(1, UPLOAD_CHUNK // max(1, store[0].nbytes))
+        for lo in range(0, n, rows):
+            self.store[lo:lo + rows].copy_(torch.from_numpy(store[lo:lo + rows]))
+        self.lut = dataset.byte_table().to(self.device)
+
+    @staticmethod
+    def _refuse_above(need: int, max_bytes: int) -> None:
+        if need > max_bytes:
+            raise MemoryError(f"the decoded image store takes {need} bytes, above max_bytes={max_bytes}: train with the default loaders "
+                              f"(cache 'none') or raise max_bytes")
+
+    def __len__(self):
+        return self.store.shape[0]
+
+    def batch(self, idx):
+        """(images float32 [B, 3, H, W] on the device, labels int64 [B] on the CPU) for CPU indices idx [B]."""
+        from . import _lib
+        idx = check_indices(idx, len(self))
+        B, (H, W) = idx.numel(), self.size
+        idx_dev = idx.to(torch.int32).to(self.device)
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.load().nd_img_gather_u8(_lib.ptr(self.store), len(self), self.store.shape[1], H * W, _lib.ptr(idx_dev), B,
+                                                _lib.ptr(self.lut), _lib.ptr(out), _lib.current_stream_ptr(self.device)), "nd_img_gather_u8")
+        return out, self.targets[idx]
+
+    def loader(self, batch_size: int, shuffle: bool = False, generator=None, drop_last: bool = False) -> IndexBatchLoader:
+        return IndexBatchLoader(self, batch_size, shuffle=shuffle, generator=generator, drop_last=drop_last)
 
 
 ATTACKS = ("FGSM", "PGD", "BIM", "AUTOPGD", "CW")

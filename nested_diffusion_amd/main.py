@@ -78,6 +78,10 @@ def build_parser() -> argparse.ArgumentParser:
     # additions of this build (no reference counterpart)
     p.add_argument("--synthetic_batches", type=int, default=0, help="run on N synthetic test batches instead of a disk dataset")
     p.add_argument("--mc_trials", type=int, default=20, help="Monte-Carlo trials per member (hard-coded 20 in the reference)")
+    p.add_argument("--train_cache", type=str, default="none", choices=["none", "device"],
+                   help="training (--mlp_idx k): 'device' decodes every image once, keeps both splits on the GPU as bytes and gathers each "
+                        "batch there (same batches, same weights); 'none' decodes every epoch in a DataLoader")
+    p.add_argument("--cache_dir", type=str, default=None, help="with --train_cache device: keep the decoded sets here and reuse them in later runs")
     return p
 
 

@@ -181,7 +181,8 @@ class Diffusion(object):
         commented out, :890-908), and Adam's moments of the 150528 x 4096 layer would triple the file.  No EMA shadow is kept: the
         reference updates one and never reads it.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
         (default: <dataroot>/training shuffled in batches of training.batch_size, <dataroot>/validation in batches of
-        testing.batch_size, drop_last).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
+        testing.batch_size, drop_last; with --train_cache device the same batches in the same order from data.DeviceImageSet, decoded once
+        and gathered on the GPU, --cache_dir keeping the decoded sets for later runs).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
         from .train_diffusion import NoiseEstimatorTrainer, antithetic_timesteps, cast_label_to_one_hot_and_prototype, lr_at
         args, config = self.args, self.config
         K = len(self.cond_pred_model.mlps)
@@ -201,14 +202,25 @@ class Diffusion(object):
         print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
         B_valid = config.testing.batch_size
         if train_loader is None or valid_loader is None:
-            from .data import ImageFolderDataset
+            from .data import CACHE_CHOICES, DeviceImageSet, ImageFolderDataset, cache_file
             workers = int(getattr(config.data, "num_workers", 0) or 0)
+            cache, cache_dir = getattr(args, "train_cache", None) or "none", getattr(args, "cache_dir", None)
+            if cache not in CACHE_CHOICES:
+                raise ValueError(f"train_cache must be one of {CACHE_CHOICES} (train_cache={cache!r})")
+            side = int(round((config.model.data_dim / 3) ** 0.5))          # 224 for data_dim = 150528 (3 x 224 x 224)
+            size = (side, side) if 3 * side * side == config.model.data_dim else (224, 224)
+
+            def loader(split, batch_size, **kw):
+                """the DataLoader of the split, or with --train_cache device the same batches from a device-resident set"""
+                ds = ImageFolderDataset(os.path.join(config.data.dataroot, split), config.data.dataset, args.preprocess, size)
+                if cache == "device":
+                    return DeviceImageSet(ds, self.device, cache_path=cache_file(cache_dir, split, ds)).loader(batch_size, **kw)
+                return torch.utils.data.DataLoader(ds, batch_size=batch_size, num_workers=workers, **kw)
+
             if train_loader is None:
-                ds = ImageFolderDataset(os.path.join(config.data.dataroot, "training"), config.data.dataset, args.preprocess)
-                train_loader = torch.utils.data.DataLoader(ds, batch_size=config.training.batch_size, shuffle=True, num_workers=workers)
+                train_loader = loader("training", config.training.batch_size, shuffle=True)
             if valid_loader is None:
-                ds = ImageFolderDataset(os.path.join(config.data.dataroot, "validation"), config.data.dataset, args.preprocess)
-                valid_loader = torch.utils.data.DataLoader(ds, batch_size=B_valid, shuffle=False, num_workers=workers, drop_last=True)
+                valid_loader = loader("validation", B_valid, shuffle=False, drop_last=True)
         trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0)
         engine: Optional[EnsembleEngine] = None
         n_epochs, freq = config.training.n_epochs, config.training.validation_freq

@@ -20,6 +20,7 @@ import torch
 
 from . import _trainer, ops
 from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
+from .data import CACHE_CHOICES, DeviceImageSet, ImageFolderDataset, cache_file
 from .mapping import Classifier, VisionTransformer, load_pickled
 
 MAX_BATCH = ops.LINEAR_BWD_MAX_M      # rows per training step: one nd_linear_bwd / nd_linear_wgrad_adam launch
@@ -120,7 +121,7 @@ class MappingTrainer(EpochTrainer):
 
 def build_parser() -> argparse.ArgumentParser:
     """The reference's flag names, types and choices (the two datasets this package has a loader for), plus --vit, --out, --epochs and
-    --batch_size."""
+    --batch_size, and the training input's --cache, --cache_dir and --workers."""
     ap = argparse.ArgumentParser(prog="python -m nested_diffusion_amd.train_mapping",
                                  description="Train one mapping MLP over a frozen ViT prefix on the GPU (fused HIP weight gradient + Adam).")
     ap.add_argument("--seed", type=int, default=None, help="seed of the weight draw and of the training loader's shuffle (default: drawn at random)")
@@ -132,6 +133,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--out", required=True, help="directory that receives MLPs/block_<mn_idx>.pth")
     ap.add_argument("--epochs", type=int, default=None, help="default: per dataset (DATASET_DEFAULTS)")
     ap.add_argument("--batch_size", type=int, default=None, help=f"training batch, at most {MAX_BATCH}; default: per dataset (DATASET_DEFAULTS)")
+    add_cache_flags(ap)
     return ap
 
 
@@ -140,15 +142,40 @@ def resolve_settings(args) -> dict:
     return _trainer.resolve_settings(args, DATASET_DEFAULTS, MAX_BATCH)
 
 
-def make_loaders(root_dir: str, dataset: str, preprocess: str, batch_size: int, seed: int):
+def add_cache_flags(ap: argparse.ArgumentParser) -> None:
+    """--cache / --cache_dir / --workers: the training input of train_mapping and train_transformer.  A flag that is not given leaves no
+    attribute behind (the namespace of a run without them is what it was); cache_settings reads them with their defaults."""
+    ap.add_argument("--cache", default=argparse.SUPPRESS, choices=list(CACHE_CHOICES),
+                    help="'device': decode every image once, keep both splits on the GPU as bytes and gather each batch there "
+                         "(data.DeviceImageSet; same batches, same weights); 'none' (default): a DataLoader decodes every epoch")
+    ap.add_argument("--cache_dir", default=argparse.SUPPRESS, help="with --cache device: keep the decoded sets in this directory and reuse them in later runs")
+    ap.add_argument("--workers", type=int, default=argparse.SUPPRESS,
+                    help="with --cache device: decode threads, at most 16 (default: the CPUs this process may use, at most 16)")
+
+
+def cache_settings(args) -> dict:
+    """make_loaders' cache / cache_dir / workers from a parsed command line: 'none', None, None unless given."""
+    return dict(cache=getattr(args, "cache", "none"), cache_dir=getattr(args, "cache_dir", None), workers=getattr(args, "workers", None))
+
+
+def make_loaders(root_dir: str, dataset: str, preprocess: str, batch_size: int, seed: int, cache: str = "none", cache_dir: Optional[str] = None,
+                 workers: Optional[int] = None, device=None, image_size=(224, 224)):
     """(training loader, shuffled under the seed; validation loader, batches of VALID_BATCH in file order).  Unlike the reference's validation
     loader (drop_last=True) the last partial batch is KEPT: the reference divides by the full dataset length either way, so on a set whose
     size is no multiple of 70 its reported validation accuracy leaves the tail out of the numerator; here every image counts.  The
-    accuracy, and with it the epoch whose weights are saved, can therefore differ from the reference's on such a set."""
-    from .data import ImageFolderDataset
-    train = ImageFolderDataset(os.path.join(root_dir, TRAIN_DIR), dataset, preprocess)
-    valid = ImageFolderDataset(os.path.join(root_dir, VALID_DIR), dataset, preprocess)
+    accuracy, and with it the epoch whose weights are saved, can therefore differ from the reference's on such a set.
+    cache='device': the same batches in the same order from data.DeviceImageSet (decoded once by `workers` threads, held on `device`,
+    default 'cuda'; images arrive on the device, labels on the CPU); cache_dir keeps the decoded sets as
+    <cache_dir>/<split>_<preprocess>_<H>x<W>.npz for later runs."""
+    if cache not in CACHE_CHOICES:
+        raise ValueError(f"cache must be one of {CACHE_CHOICES} (cache={cache!r})")
+    train = ImageFolderDataset(os.path.join(root_dir, TRAIN_DIR), dataset, preprocess, image_size)
+    valid = ImageFolderDataset(os.path.join(root_dir, VALID_DIR), dataset, preprocess, image_size)
     g = torch.Generator().manual_seed(int(seed))
+    if cache == "device":
+        sets = [DeviceImageSet(ds, device or "cuda", workers=workers, cache_path=cache_file(cache_dir, split, ds))
+                for split, ds in ((TRAIN_DIR, train), (VALID_DIR, valid))]
+        return sets[0].loader(batch_size, shuffle=True, generator=g), sets[1].loader(VALID_BATCH, shuffle=False)
     return (torch.utils.data.DataLoader(train, batch_size=batch_size, shuffle=True, generator=g),
             torch.utils.data.DataLoader(valid, batch_size=VALID_BATCH, shuffle=False))
 
@@ -161,7 +188,7 @@ def main(argv=None) -> dict:
     print(f"Training Mapping Network {args.mn_idx} on {args.root_dir}")
     vit_sd = load_pickled(args.vit)
     vit = VisionTransformer(vit_sd, max(1, vit_sd["patch_embed.proj.weight"].shape[0] // 64), "cuda")
-    train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"])
+    train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"], **cache_settings(args))
     trainer = MappingTrainer(vit, args.mn_idx, num_classes=s["num_classes"], lr=s["lr"], step_size=s["step_size"], gamma=s["gamma"],
                              seed=s["seed"])
     return trainer.fit(train_loader, valid_loader, s["epochs"], args.out)

@@ -25,7 +25,7 @@ import torch
 from . import _trainer, ops
 from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
 from .mapping import LN_EPS, VisionTransformer, load_pickled, require_fp32_split
-from .train_mapping import TRAIN_DIR, VALID_DIR, make_loaders
+from .train_mapping import TRAIN_DIR, VALID_DIR, add_cache_flags, cache_settings, make_loaders
 
 # mapping/train_transformer.py:47-49, 95-97 (the two datasets this package has a loader for)
 DATASET_DEFAULTS = {
@@ -239,7 +239,7 @@ class ViTTrainer(EpochTrainer):
 
 def build_parser() -> argparse.ArgumentParser:
     """The reference's flag names, types and choices (the two datasets this package has a loader for; model_type is always 'vit'), plus
-    --out, --init, --epochs and --batch_size."""
+    --out, --init, --epochs and --batch_size, and the training input's --cache, --cache_dir and --workers."""
     ap = argparse.ArgumentParser(prog="python -m nested_diffusion_amd.train_transformer",
                                  description="Train the ViT on the GPU (HIP backward chain, fused weight gradient + AdamW).")
     ap.add_argument("--seed", type=int, default=None, help="seed of the weight draw and of the training loader's shuffle (default: drawn at random)")
@@ -250,6 +250,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--init", default=None, help="start from this ViT checkpoint (a state dict or a whole-module pickle) instead of a fresh model")
     ap.add_argument("--epochs", type=int, default=None, help="default: per dataset (DATASET_DEFAULTS)")
     ap.add_argument("--batch_size", type=int, default=None, help="training batch; default: per dataset (DATASET_DEFAULTS)")
+    add_cache_flags(ap)
     return ap
 
 
@@ -268,7 +269,7 @@ def main(argv=None) -> dict:
     heads = max(1, sd["patch_embed.proj.weight"].shape[0] // 64) if sd is not None else 12
     trainer = ViTTrainer(sd, num_classes=s["num_classes"], num_heads=heads, lr=s["lr"], weight_decay=s["weight_decay"],
                          step_size=s["step_size"], gamma=s["gamma"], seed=s["seed"])
-    train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"])
+    train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"], **cache_settings(args))
     return trainer.fit(train_loader, valid_loader, s["epochs"], args.out, args.dataset)
 
 
