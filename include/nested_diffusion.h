@@ -312,6 +312,12 @@ int nd_aggregate(const float *samples_dev, float *prob_out_dev, int64_t *vote_ou
  * first image), and the batch counter -- kept on the device, advanced by the sampler itself -- makes successive batches
  * differ.  nd_seed resets it to 0.  Synchronises the device (rare: once per run). */
 int nd_seed(nd_handle h, uint64_t seed, uint32_t first_image);
+/* The generator's device-resident state for a resumable run: out[0] = the seed, out[1] = batch counter | first_image << 32.
+ * nd_rng_state reads it once every sampling loop enqueued so far has advanced the counter; nd_set_rng_state puts a state read
+ * earlier back, so the next nd_sample / nd_predict_batch draws what it would have drawn then.  Both synchronise the device as
+ * nd_seed does (rare: once per snapshot / resume); a NULL handle or pointer is ND_ERR_ARG. */
+int nd_rng_state(nd_handle h, uint64_t out[2]);
+int nd_set_rng_state(nd_handle h, const uint64_t in[2]);
 /* The same generator as a standalone operator (tests, known-answer checks): out_dev [n_members, T, mc*B, C], row = trial*B + b. */
 int nd_philox_normal(float *out_dev, int n_members, int T, int B, int mc, int C, uint64_t seed, uint32_t batch_counter,
                      uint32_t first_image, void *stream);

@@ -122,6 +122,8 @@ SIGNATURES = {
     "nd_resident_weight_bytes": (C.c_longlong, [_vp, _i]),
     "nd_member_buffer": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "nd_seed": (_i, [_vp, C.c_uint64, C.c_uint32]),
+    "nd_rng_state": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "nd_set_rng_state": (_i, [_vp, C.POINTER(C.c_uint64)]),
     "nd_philox_normal": (_i, [_vp, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
     "nd_philox_raw": (_i, [_vp, _vp, _i, C.c_uint32, C.c_uint32, _vp]),
     "nd_cond_workspace_bytes": (_sz, [C.POINTER(NdCondConfig)]),

@@ -9,7 +9,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, snapshot
 
 
 def step_lr(lr: float, epoch: int, step_size: int, gamma: float) -> float:
@@ -33,7 +33,11 @@ def resolve_settings(args, defaults: dict, max_batch: Optional[int] = None) -> d
 
 class EpochTrainer:
     """The loop around a trainer's step.  A subclass sets device, base_lr, step_size, gamma and epoch (scheduler steps taken) and supplies
-    step(images, labels) -> (loss_sum, n_correct) as device scalars, logits(images), _labels(labels, B) and state_dict()."""
+    step(images, labels) -> (loss_sum, n_correct) as device scalars, logits(images), _labels(labels, B) and state_dict(); for snapshots
+    also training_state() and load_training_state(state), whose 'meta' carries run_meta (what the loop knows of the run: the dataset,
+    the batch size, the training loader's length, the epoch count)."""
+
+    run_meta: dict = {}
 
     @property
     def lr(self) -> float:
@@ -71,12 +75,30 @@ class EpochTrainer:
             raise ValueError("train_epoch: the loader is empty")
         return float(loss_sum) / n, int(correct) / n
 
-    def _fit(self, train_loader, valid_loader, epochs: int, path: str, title: str) -> dict:
+    def _fit(self, train_loader, valid_loader, epochs: int, path: str, title: str, snapshot_path: Optional[str] = None,
+             snapshot_epochs: int = 0, resume: bool = False) -> dict:
         """mapping/train_mapping.py:92-165, mapping/train_transformer.py:104-172: train epoch, validate, print the two lines, save to
         `path` on a strictly better validation accuracy, then the scheduler step; at the end the line '<title> best train Acc ...'.
-        Returns {'best_acc', 'best_train_acc', 'saved_epochs', 'path'}."""
-        best_acc, best_train_acc, saved = 0.0, 0.0, []
-        for epoch in range(int(epochs)):
+        Returns {'best_acc', 'best_train_acc', 'saved_epochs', 'path'}.
+        snapshot_path with snapshot_epochs N > 0: after every N-th epoch's scheduler step, and after the last epoch's, the file receives
+        {'trainer': training_state(), 'loop': {'next_epoch', 'best_acc', 'best_train_acc', 'saved_epochs'}, 'rng': snapshot.rng_state}
+        (snapshot.atomic_save).  resume: the run starts from that file at the top of epoch 'next_epoch', with every generator where it
+        was; the returned dict then covers the earlier epochs too.  The subclass supplies training_state / load_training_state."""
+        best_acc, best_train_acc, saved, first = 0.0, 0.0, [], 0
+        self.run_meta = dict(self.run_meta, batch_size=snapshot.loader_batch_size(train_loader),
+                             train_batches=len(train_loader) if hasattr(train_loader, "__len__") else None, epochs=int(epochs))
+        if resume:
+            if snapshot_path is None:
+                raise ValueError("resume needs a snapshot_path")
+            snap = snapshot.read(snapshot_path)
+            self.load_training_state(snap["trainer"])
+            loop = snap["loop"]
+            first, best_acc, best_train_acc = int(loop["next_epoch"]), float(loop["best_acc"]), float(loop["best_train_acc"])
+            saved = [int(e) for e in loop["saved_epochs"]]
+            snapshot.set_rng_state(snap["rng"], self.device, train_loader)
+            del snap
+            print(f"Resumed from {snapshot_path} at epoch {first}")
+        for epoch in range(first, int(epochs)):
             tr_loss, tr_acc = self.train_epoch(train_loader)
             print(f"Epoch {epoch} Train Loss: {tr_loss:.4f} Acc: {tr_acc:.4f}")
             va_loss, va_acc = self.evaluate(valid_loader)
@@ -87,5 +109,9 @@ class EpochTrainer:
                 torch.save(self.state_dict(), path)
                 saved.append(epoch)
             self.scheduler_step()
+            if snapshot_path is not None and snapshot.due(epoch, int(epochs), int(snapshot_epochs)):
+                loop = {"next_epoch": epoch + 1, "best_acc": best_acc, "best_train_acc": best_train_acc, "saved_epochs": list(saved)}
+                snapshot.atomic_save({"trainer": self.training_state(), "loop": loop,
+                                      "rng": snapshot.rng_state(self.device, train_loader)}, snapshot_path)
         print(f"{title} best train Acc: {best_train_acc:.4f} val Acc: {best_acc:.4f}")
         return {"best_acc": best_acc, "best_train_acc": best_train_acc, "saved_epochs": saved, "path": path}

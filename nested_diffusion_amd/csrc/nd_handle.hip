@@ -180,6 +180,26 @@ extern "C" int nd_seed(nd_handle h, uint64_t seed, uint32_t first_image) {
     return ND_OK;
 }
 
+extern "C" int nd_rng_state(nd_handle h, uint64_t out[2]) {
+    if (!h || !out) return nd_set_err(ND_ERR_ARG, "handle/out is NULL");
+    if (!h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");
+    unsigned long long st[2];
+    HIP_CHECK(hipDeviceSynchronize());          // every enqueued sampling loop has advanced the batch counter
+    HIP_CHECK(hipMemcpy(st, h->rng_state, sizeof st, hipMemcpyDeviceToHost));
+    out[0] = (uint64_t)st[0];
+    out[1] = (uint64_t)st[1];
+    return ND_OK;
+}
+
+extern "C" int nd_set_rng_state(nd_handle h, const uint64_t in[2]) {
+    if (!h || !in) return nd_set_err(ND_ERR_ARG, "handle/in is NULL");
+    if (!h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");
+    const unsigned long long st[2] = {(unsigned long long)in[0], (unsigned long long)in[1]};
+    HIP_CHECK(hipDeviceSynchronize());          // as nd_seed: no sampling graph may be reading the state while it is replaced
+    HIP_CHECK(hipMemcpy(h->rng_state, st, sizeof st, hipMemcpyHostToDevice));
+    return ND_OK;
+}
+
 extern "C" int nd_set_schedule(nd_handle h, const float* alphas_dev, const float* omabs_dev, int T, void* stream) {
     if (!h || !h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");
     if (!alphas_dev || !omabs_dev) return nd_set_err(ND_ERR_ARG, "NULL schedule");

@@ -111,6 +111,20 @@ class EnsembleEngine:
         do not depend on how the batch is sharded.  Resets the batch counter."""
         check(self.lib.nd_seed(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image) & 0xFFFFFFFF), "nd_seed")
 
+    def rng_state(self) -> Tuple[int, int]:
+        """The in-library generator's state (seed, batch counter | first_image << 32) after every sampling call issued so far
+        (nd_rng_state; synchronises the device): what a training snapshot keeps of the validation noise."""
+        st = (C.c_uint64 * 2)()
+        check(self.lib.nd_rng_state(self.h, st), "nd_rng_state")
+        return int(st[0]), int(st[1])
+
+    def set_rng_state(self, state: Sequence[int]) -> None:
+        """Put a state read with rng_state() back: the next sample() / predict_batch() draws what it would have drawn then."""
+        if len(state) != 2:
+            raise ValueError(f"the generator's state is two 64-bit words (got {len(state)})")
+        st = (C.c_uint64 * 2)(int(state[0]) & 0xFFFFFFFFFFFFFFFF, int(state[1]) & 0xFFFFFFFFFFFFFFFF)
+        check(self.lib.nd_set_rng_state(self.h, st), "nd_set_rng_state")
+
     # -- compute -----------------------------------------------------------------------------
     def encode(self, x: torch.Tensor, member0: int = 0, n_members: Optional[int] = None) -> None:
         """xe = norm(encoder_x(x)) for a member range, cached in the workspace (latent_model.py:170-171)."""

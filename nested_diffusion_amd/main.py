@@ -6,8 +6,9 @@
 Same flags, YAML keys and checkpoint layout as the reference (main.py:16-161, 166-296, 299-380;
 canonical invocation testing_scripts/test.sh:24).  Implemented, with loss card_onehot_conditional and
 aux_cls.arch == 'sevit' (the shipped configs): `--test`, `--calib`, and -- with neither -- training of the noise
-estimator `--mlp_idx` on one GPU (runner.Diffusion.train); the other training / sampling flags are
-parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials.
+estimator `--mlp_idx` on one GPU (runner.Diffusion.train; `--snapshot_epochs N` keeps the whole training state in
+<log_path>/ckpt.pth and `--resume_training` continues from it); the other training / sampling flags are
+parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials, --snapshot_epochs.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N -m nested_diffusion_amd.main ...`.
 """
 from __future__ import annotations
@@ -82,6 +83,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="training (--mlp_idx k): 'device' decodes every image once, keeps both splits on the GPU as bytes and gathers each "
                         "batch there (same batches, same weights); 'none' decodes every epoch in a DataLoader")
     p.add_argument("--cache_dir", type=str, default=None, help="with --train_cache device: keep the decoded sets here and reuse them in later runs")
+    p.add_argument("--snapshot_epochs", type=int, default=argparse.SUPPRESS,
+                   help="training (--mlp_idx k): write the whole training state (weights, Adam's moments, counters, generators) to "
+                        "<log_path>/ckpt.pth every N epochs and after the last one; --resume_training continues from that file "
+                        "(default 0: never; a flag that is not given leaves no attribute behind)")
     return p
 
 

@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import ops
+from . import ops, snapshot
 from .diffusion_utils import schedule_tables
 from .engine import EnsembleEngine
 from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner, require_fp32_split
@@ -177,9 +177,13 @@ class Diffusion(object):
         validation set is sampled with the current weights (p_sample_loop in eval mode: trainer.state_dict() loaded into a one-member
         EnsembleEngine, noise drawn in the library) and the top-1 accuracy of y_0 taken; a new best writes
         <log_path>/diffu{idx}_ckpt_best_eph{epoch}_acc{acc:.4f}.pth = {'noise_estimator', 'optimizer', 'epoch'}, the layout
-        load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: nothing reads it (the reference's resume path is
-        commented out, :890-908), and Adam's moments of the 150528 x 4096 layer would triple the file.  No EMA shadow is kept: the
-        reference updates one and never reads it.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
+        load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: the best file is for inference, and Adam's moments of
+        the 150528 x 4096 layer would triple it.  The whole training state goes to <log_path>/ckpt.pth instead (the reference's
+        name, :890-908), every args.snapshot_epochs epochs and after the last: {'trainer': trainer.training_state(), 'loop':
+        {'next_epoch', 'step', 'max_accuracy', 'best', 'losses', 'accuracies'}, 'rng': snapshot.rng_state, the validation engine's
+        sampler state included}; args.resume_training continues from it at the top of epoch 'next_epoch' (a FileNotFoundError
+        names the file if there is none), with lr_at on the true epoch index, and returns the earlier epochs too.  No EMA shadow
+        is kept: the reference updates one and never reads it.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
         (default: <dataroot>/training shuffled in batches of training.batch_size, <dataroot>/validation in batches of
         testing.batch_size, drop_last; with --train_cache device the same batches in the same order from data.DeviceImageSet, decoded once
         and gathered on the GPU, --cache_dir keeping the decoded sets for later runs).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
@@ -193,12 +197,14 @@ class Diffusion(object):
             raise NotImplementedError("Diffusion.train runs on one GPU: world size > 1 is not implemented")
         if getattr(args, "train_guidance_only", False):
             raise NotImplementedError("--train_guidance_only is not implemented")
-        if getattr(args, "resume_training", False):
-            raise NotImplementedError("--resume_training is not implemented (the reference's resume path is commented out)")
         if config.diffusion.aux_cls.arch != "sevit":
             raise NotImplementedError(f"aux_cls.arch == {config.diffusion.aux_cls.arch!r}: only 'sevit' is implemented")
         if self.operand_dtype != "f32":
             raise NotImplementedError("training runs in fp32 mode: the fp16 mode is not implemented")
+        # --resume_training: the snapshot is read before anything is built, so a missing file costs nothing
+        snap_path = os.path.join(args.log_path, "ckpt.pth")                   # the reference's file name (:890-908, commented out there)
+        snapshot_epochs = int(getattr(args, "snapshot_epochs", 0) or 0)
+        snap = snapshot.read(snap_path) if getattr(args, "resume_training", False) else None
         print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
         B_valid = config.testing.batch_size
         if train_loader is None or valid_loader is None:
@@ -222,17 +228,39 @@ class Diffusion(object):
             if valid_loader is None:
                 valid_loader = loader("validation", B_valid, shuffle=False, drop_last=True)
         trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0)
+        self.trainer = trainer                     # stays reachable after the run: its training_state() is what a snapshot holds
+        batch_size = snapshot.loader_batch_size(train_loader)
+        trainer.run_meta = {"mlp_idx": int(mlp_idx), "dataset": config.data.dataset, "train_batches": len(train_loader),
+                            "batch_size": config.training.batch_size if batch_size is None else batch_size,
+                            "epochs": int(config.training.n_epochs)}
         engine: Optional[EnsembleEngine] = None
         n_epochs, freq = config.training.n_epochs, config.training.validation_freq
         log_freq = getattr(config.training, "logging_freq", 0) or 0
-        max_accuracy, step, best = 0.0, 0, None
+        max_accuracy, step, best, first_epoch = 0.0, 0, None, 0
         losses, accuracies = [], {}
 
         def yhat_of(images):
             logits = self.compute_guiding_prediction(images, include_full_vit=mlp_idx == -1)
             return ops.softmax_rows(logits[mlp_idx].contiguous())            # :955-958
 
-        for epoch in range(n_epochs):
+        def validation_engine():
+            eng = EnsembleEngine(config.data.num_classes, config.model.data_dim, config.model.hidden_dim, config.model.feature_dim,
+                                 self.num_timesteps, n_members=1, max_batch=B_valid, max_rows=B_valid, device=self.device)
+            eng.set_schedule(self.alphas, self.one_minus_alphas_bar_sqrt)
+            eng.seed(self.seed or 0)
+            return eng
+
+        if snap is not None:
+            trainer.load_training_state(snap["trainer"])
+            loop = snap["loop"]
+            first_epoch, step, max_accuracy, best = int(loop["next_epoch"]), int(loop["step"]), float(loop["max_accuracy"]), loop["best"]
+            losses, accuracies = [float(v) for v in loop["losses"]], {int(k): float(v) for k, v in loop["accuracies"].items()}
+            if snap["rng"].get("engine") is not None:                        # the run had validated: its sampler state goes back
+                engine = validation_engine()
+            snapshot.set_rng_state(snap["rng"], self.device, train_loader, engine)
+            snap = None
+            logging.info(f"Resumed from {snap_path} at epoch {first_epoch}, step {step}")
+        for epoch in range(first_epoch, n_epochs):
             loss = None
             for i, (x_raw, labels) in enumerate(train_loader):
                 x = x_raw.to(self.device, torch.float32).contiguous()
@@ -253,10 +281,7 @@ class Diffusion(object):
             logging.info(f"epoch: {epoch}, step: {step}, Noise Estimation loss: {losses[-1]}")
             if epoch % freq == 0 or epoch + 1 == n_epochs:                        # :1054-1055
                 if engine is None:
-                    engine = EnsembleEngine(config.data.num_classes, config.model.data_dim, config.model.hidden_dim, config.model.feature_dim,
-                                            self.num_timesteps, n_members=1, max_batch=B_valid, max_rows=B_valid, device=self.device)
-                    engine.set_schedule(self.alphas, self.one_minus_alphas_bar_sqrt)
-                    engine.seed(self.seed or 0)
+                    engine = validation_engine()
                 engine.load_member(0, trainer.state_dict(cpu=False))
                 acc_sum, n_batches = 0.0, 0
                 for images_raw, target in valid_loader:
@@ -279,6 +304,11 @@ class Diffusion(object):
                 max_accuracy = max(max_accuracy, acc_avg)
                 logging.info(f"epoch: {epoch}, step: {step}, Average diffusion {mlp_idx} accuracy: {acc_avg}%, "
                              f"Max diffusion {mlp_idx} accuracy: {max_accuracy:.2f}%, ")
+            if snapshot.due(epoch, n_epochs, snapshot_epochs):
+                loop = {"next_epoch": epoch + 1, "step": step, "max_accuracy": max_accuracy, "best": best, "losses": list(losses),
+                        "accuracies": dict(accuracies)}
+                snapshot.atomic_save({"trainer": trainer.training_state(), "loop": loop,
+                                      "rng": snapshot.rng_state(self.device, train_loader, engine)}, snap_path)
         return {"losses": losses, "accuracies": accuracies, "best": best}
 
     # ---- the hot path (:749-794) --------------------------------------------------------------

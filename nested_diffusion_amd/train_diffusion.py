@@ -15,8 +15,9 @@ and sums in double (include/nested_diffusion.h says why).  Nothing is read back 
 CPU until check_step_args has passed them, and the schedule coefficients of a batch are gathered there.
 
 Left out: the EMA shadow.  The reference updates one on every step (:1007-1011) but never reads it -- the checkpoint saves
-noise_estimator.state_dict() (:1120) -- so it has no effect on anything the reference writes.  Also out of scope: resuming,
-train_guidance_only, more than one GPU, the fp16 mode."""
+noise_estimator.state_dict() (:1120) -- so it has no effect on anything the reference writes.  Also out of scope:
+train_guidance_only, more than one GPU, the fp16 mode.  training_state() / load_training_state() carry a run across an interruption
+(snapshot.py; Diffusion.train writes and reads the file)."""
 from __future__ import annotations
 
 import math
@@ -24,7 +25,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import ops, snapshot
 from .diffusion_utils import schedule_tables
 from .latent_model import LIN1_K, check_member_dims, member_shapes, pad_lin1
 
@@ -128,6 +129,7 @@ class NoiseEstimatorTrainer:
         clip = getattr(optim, "grad_clip", 1.0)
         self.grad_clip = float(clip)
         self.t = 0                                                                  # Adam steps taken = num_batches_tracked
+        self.run_meta: Dict[str, object] = {}      # what the loop adds to a snapshot's meta: mlp_idx, dataset, batch_size, train_batches, epochs
         # the schedule tables q_sample reads (classification_train_separately.py:215-226), on the CPU: a batch's rows are gathered there
         tables = schedule_tables(getattr(config.diffusion, "beta_schedule", "linear"), T, getattr(config.diffusion, "beta_start", 1e-4),
                                  getattr(config.diffusion, "beta_end", 0.02))
@@ -294,3 +296,56 @@ class NoiseEstimatorTrainer:
                 sd[name + ".running_var"] = self.buf[name + ".running_var"].clone()
                 sd[name + ".num_batches_tracked"] = torch.tensor(self.batches_tracked, dtype=torch.int64)
         return {k: (v.detach().cpu() if cpu else v.detach().to(self.device)) for k, v in sd.items()}
+
+    # ---- the whole training state, for snapshots (snapshot.py) ---------------------------------------------------------------------
+    def _meta(self) -> dict:
+        return dict({"format": snapshot.FORMAT, "kind": "noise_estimator", "num_classes": self.C, "data_dim": self.D, "hidden_dim": self.H,
+                     "feature_dim": self.F, "timesteps": self.T}, **self.run_meta)
+
+    def training_state(self) -> dict:
+        """Everything a continued run needs, on the CPU, row-major, in the reference's keys and shapes: {'meta', 'p', 'm', 'v' (Adam's
+        moments under the parameters' keys; lin1.lin.weight cut to [F, 2C] in all three), 'buf' (the running statistics), 't',
+        'batches_tracked', 'lr'}.  One tensor is unpacked, copied out and released at a time: the device holds at most one row-major
+        weight beside the model."""
+        def out(k, q):
+            w = q.unpack() if isinstance(q, ops.PackedWeight) else q
+            if k == "lin1.lin.weight":
+                w = w[:, :2 * self.C]
+            return w.detach().contiguous().cpu()
+
+        state = {"meta": self._meta()}
+        for which, src in (("p", self.p), ("m", self.m), ("v", self.v)):
+            state[which] = {k: out(k, src[k]) for k in PARAM_KEYS}
+        state["buf"] = {k: b.detach().cpu().clone() for k, b in self.buf.items()}
+        state.update(t=int(self.t), batches_tracked=int(self.batches_tracked), lr=float(self.lr))
+        return state
+
+    def load_training_state(self, state: dict) -> None:
+        """training_state() of a run with this run's meta (snapshot.check_meta: a ValueError names the field that differs), put back
+        bit for bit: the packed images are rebuilt from the row-major tensors (PackedWeight: padding rows zero, as they were), one tensor
+        at a time.  Everything is checked before the first tensor of this trainer is replaced."""
+        snapshot.check_meta(state.get("meta"), self._meta())
+        shapes = self.shapes()
+        for which in ("p", "m", "v"):
+            for k in PARAM_KEYS:
+                if k not in state[which]:
+                    raise KeyError(f"the snapshot's '{which}' is missing '{k}'")
+                if tuple(state[which][k].shape) != shapes[k]:
+                    raise ValueError(f"{which}['{k}'] has shape {tuple(state[which][k].shape)}, expected {shapes[k]}")
+        for k, b in self.buf.items():
+            if k not in state["buf"] or tuple(state["buf"][k].shape) != tuple(b.shape):
+                raise ValueError(f"buf['{k}'] is missing or has another shape than {tuple(b.shape)}")
+        for which, dst in (("p", self.p), ("m", self.m), ("v", self.v)):
+            for k in PARAM_KEYS:
+                w = state[which][k].detach().to(self.device, torch.float32).contiguous()
+                if k == "lin1.lin.weight":
+                    w = pad_lin1(w)
+                if k in PACKED_KEYS:
+                    dst[k] = None                            # the old image goes before the new one is built
+                    dst[k] = ops.PackedWeight(w)
+                else:
+                    dst[k].copy_(w)
+                del w
+        for k, b in self.buf.items():
+            b.copy_(state["buf"][k])
+        self.t, self.batches_tracked, self.lr = int(state["t"]), int(state["batches_tracked"]), float(state["lr"])

@@ -8,7 +8,8 @@ weight gradient tile by tile and apply Adam to the packed images in place.  No g
 exists at any point; nothing is read back inside a step.
 
     python -m nested_diffusion_amd.train_mapping --dataset ChestXRay --root_dir <data> --mn_idx 0 --vit <vit .pth> --out <dir>
-writes <dir>/MLPs/block_<mn_idx>.pth (a plain state dict: mapping.load_pickled / load_conditioner read it)."""
+writes <dir>/MLPs/block_<mn_idx>.pth (a plain state dict: mapping.load_pickled / load_conditioner read it).  --snapshot_epochs N keeps the
+whole training state in <dir>/MLPs/block_<mn_idx>.ckpt (snapshot.py) and --resume continues from it."""
 from __future__ import annotations
 
 import argparse
@@ -18,7 +19,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import _trainer, ops
+from . import _trainer, ops, snapshot
 from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
 from .data import CACHE_CHOICES, DeviceImageSet, ImageFolderDataset, cache_file
 from .mapping import Classifier, VisionTransformer, load_pickled
@@ -47,6 +48,7 @@ class MappingTrainer(EpochTrainer):
         self.vit, self.mn_idx, self.device = vit, int(mn_idx), vit.device
         self.base_lr, self.step_size, self.gamma = float(lr), int(step_size), float(gamma)
         self.epoch, self.t = 0, 0                           # scheduler steps taken, Adam steps taken
+        self.run_meta: Dict[str, object] = {}               # what fit() adds to a snapshot's meta: dataset, batch_size, train_batches, epochs
         if in_features is None:
             in_features = (224 // vit.patch) ** 2 * vit.embed_dim       # vit_base_patch16_224: 196 x 768 = 150528
         dims = [int(in_features), *[int(h) for h in hidden], int(num_classes)]
@@ -58,6 +60,7 @@ class MappingTrainer(EpochTrainer):
             sd[f"linear{i + 1}.weight"] = torch.empty(dims[i + 1], dims[i], dtype=torch.float32, device=self.device).uniform_(-bound, bound, generator=gen)
             sd[f"linear{i + 1}.bias"] = torch.empty(dims[i + 1], dtype=torch.float32, device=self.device).uniform_(-bound, bound, generator=gen)
         self.model = Classifier(sd, self.device)
+        self.dims = dims
         del sd
         p = self.model.p
         self.m = {k: (t.zeros_like() if isinstance(t, ops.PackedWeight) else torch.zeros_like(t)) for k, t in p.items()}
@@ -114,9 +117,52 @@ class MappingTrainer(EpochTrainer):
         """The reference's keys linear{1..4}.{weight,bias}, weights unpacked to [N, K], on the CPU."""
         return {k: (t.unpack() if isinstance(t, ops.PackedWeight) else t).detach().cpu().clone() for k, t in self.model.p.items()}
 
-    def fit(self, train_loader, valid_loader, epochs: int, out_dir: str) -> dict:
-        """mapping/train_mapping.py:92-165 (EpochTrainer._fit), saving <out_dir>/MLPs/block_<mn_idx>.pth."""
-        return self._fit(train_loader, valid_loader, epochs, os.path.join(out_dir, "MLPs", f"block_{self.mn_idx}.pth"), f"MLP {self.mn_idx}")
+    # ---- the whole training state, for snapshots (snapshot.py) ---------------------------------------------------------------------
+    def _meta(self) -> dict:
+        return dict({"format": snapshot.FORMAT, "kind": "mapping", "mn_idx": self.mn_idx, "in_features": self.dims[0], "hidden": self.dims[1:4],
+                     "num_classes": self.dims[4]}, **self.run_meta)
+
+    def training_state(self) -> dict:
+        """{'meta', 'p', 'm', 'v' (Adam's moments under the parameters' keys), 't', 'epoch'}: on the CPU, row-major, the reference's keys
+        and shapes.  One image is unpacked, copied out and released at a time."""
+        out = lambda q: (q.unpack() if isinstance(q, ops.PackedWeight) else q).detach().cpu()    # noqa: E731
+        state = {"meta": self._meta()}
+        for which, src in (("p", self.model.p), ("m", self.m), ("v", self.v)):
+            state[which] = {k: out(src[k]) for k in Classifier.KEYS}
+        state.update(t=int(self.t), epoch=int(self.epoch))
+        return state
+
+    def load_training_state(self, state: dict) -> None:
+        """training_state() of a run with this run's meta (snapshot.check_meta: a ValueError names the field that differs), put back bit
+        for bit; the packed images are rebuilt from the row-major tensors, one at a time, after every shape has been checked."""
+        snapshot.check_meta(state.get("meta"), self._meta())
+        for which in ("p", "m", "v"):
+            for i in range(4):
+                for k, shape in ((f"linear{i + 1}.weight", (self.dims[i + 1], self.dims[i])), (f"linear{i + 1}.bias", (self.dims[i + 1],))):
+                    if k not in state[which] or tuple(state[which][k].shape) != shape:
+                        raise ValueError(f"{which}['{k}'] is missing or has another shape than {shape}")
+        for which, dst in (("p", self.model.p), ("m", self.m), ("v", self.v)):
+            for k in Classifier.KEYS:
+                w = state[which][k].detach().to(self.device, torch.float32).contiguous()
+                if isinstance(dst[k], ops.PackedWeight):
+                    dst[k] = None                            # the old image goes before the new one is built
+                    dst[k] = ops.PackedWeight(w)
+                else:
+                    dst[k].copy_(w)
+                del w
+        self.t, self.epoch = int(state["t"]), int(state["epoch"])
+
+    def fit(self, train_loader, valid_loader, epochs: int, out_dir: str, snapshot_path: Optional[str] = None, snapshot_epochs: int = 0,
+            resume: bool = False, dataset: Optional[str] = None) -> dict:
+        """mapping/train_mapping.py:92-165 (EpochTrainer._fit), saving <out_dir>/MLPs/block_<mn_idx>.pth.  snapshot_epochs N: the whole
+        training state goes to snapshot_path (default <out_dir>/MLPs/block_<mn_idx>.ckpt) every N epochs and after the last; resume: the
+        run continues from that file."""
+        path = os.path.join(out_dir, "MLPs", f"block_{self.mn_idx}.pth")
+        if snapshot_path is None and (snapshot_epochs or resume):
+            snapshot_path = path[:-4] + ".ckpt"
+        self.run_meta = dict(self.run_meta, dataset=dataset)
+        return self._fit(train_loader, valid_loader, epochs, path, f"MLP {self.mn_idx}", snapshot_path=snapshot_path,
+                         snapshot_epochs=snapshot_epochs, resume=resume)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -134,6 +180,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--epochs", type=int, default=None, help="default: per dataset (DATASET_DEFAULTS)")
     ap.add_argument("--batch_size", type=int, default=None, help=f"training batch, at most {MAX_BATCH}; default: per dataset (DATASET_DEFAULTS)")
     add_cache_flags(ap)
+    add_snapshot_flags(ap, "<out>/MLPs/block_<mn_idx>.ckpt")
     return ap
 
 
@@ -151,6 +198,24 @@ def add_cache_flags(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--cache_dir", default=argparse.SUPPRESS, help="with --cache device: keep the decoded sets in this directory and reuse them in later runs")
     ap.add_argument("--workers", type=int, default=argparse.SUPPRESS,
                     help="with --cache device: decode threads, at most 16 (default: the CPUs this process may use, at most 16)")
+
+
+def add_snapshot_flags(ap: argparse.ArgumentParser, where: str) -> None:
+    """--snapshot_epochs / --resume of train_mapping and train_transformer; like the cache flags, a flag that is not given leaves no
+    attribute behind."""
+    ap.add_argument("--snapshot_epochs", type=int, default=argparse.SUPPRESS,
+                    help=f"write the whole training state (weights, Adam's moments, counters, generators) to {where} every N epochs and "
+                         f"after the last one (default 0: never)")
+    ap.add_argument("--resume", action="store_true", default=argparse.SUPPRESS,
+                    help=f"continue the run whose state is in {where} (weights, counters and the shuffle's position come from it): same dataset and batch size; --epochs may be larger")
+
+
+def snapshot_settings(args) -> dict:
+    """fit's snapshot_epochs / resume from a parsed command line: 0 and False unless given."""
+    n = int(getattr(args, "snapshot_epochs", 0))
+    if n < 0:
+        raise SystemExit(f"--snapshot_epochs must be at least 0 (got {n})")
+    return dict(snapshot_epochs=n, resume=bool(getattr(args, "resume", False)))
 
 
 def cache_settings(args) -> dict:
@@ -191,7 +256,7 @@ def main(argv=None) -> dict:
     train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"], **cache_settings(args))
     trainer = MappingTrainer(vit, args.mn_idx, num_classes=s["num_classes"], lr=s["lr"], step_size=s["step_size"], gamma=s["gamma"],
                              seed=s["seed"])
-    return trainer.fit(train_loader, valid_loader, s["epochs"], args.out)
+    return trainer.fit(train_loader, valid_loader, s["epochs"], args.out, dataset=args.dataset, **snapshot_settings(args))
 
 
 if __name__ == "__main__":

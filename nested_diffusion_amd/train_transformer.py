@@ -12,7 +12,8 @@ back inside a step.
 
     python -m nested_diffusion_amd.train_transformer --dataset ChestXRay --root_dir <data> --out <dir>
 writes <dir>/vit_base_patch16_224_<Dataset>.pth (a plain timm-keyed state dict: mapping.load_pickled / load_conditioner and
-train_mapping --vit read it)."""
+train_mapping --vit read it).  --snapshot_epochs N keeps the whole training state in <dir>/vit_base_patch16_224_<Dataset>.ckpt (snapshot.py)
+and --resume continues from it."""
 from __future__ import annotations
 
 import argparse
@@ -22,10 +23,10 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _trainer, ops
+from . import _trainer, ops, snapshot
 from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
 from .mapping import LN_EPS, VisionTransformer, load_pickled, require_fp32_split
-from .train_mapping import TRAIN_DIR, VALID_DIR, add_cache_flags, cache_settings, make_loaders
+from .train_mapping import TRAIN_DIR, VALID_DIR, add_cache_flags, add_snapshot_flags, cache_settings, make_loaders, snapshot_settings
 
 # mapping/train_transformer.py:47-49, 95-97 (the two datasets this package has a loader for)
 DATASET_DEFAULTS = {
@@ -108,6 +109,7 @@ class ViTTrainer(EpochTrainer):
         self.device = self.vit.device
         self.base_lr, self.weight_decay, self.step_size, self.gamma = float(lr), float(weight_decay), int(step_size), float(gamma)
         self.epoch, self.t = 0, 0                               # scheduler steps taken, AdamW steps taken
+        self.run_meta: Dict[str, object] = {}                   # what fit() adds to a snapshot's meta: dataset, batch_size, train_batches, epochs
         p = self.vit.p
         # the row-major fp32 masters of the weights the ViT holds as images only; every other parameter is its own master in vit.p
         self.master = {k: sd[k].detach().to(self.device, torch.float32).contiguous().clone() for k, t in p.items()
@@ -232,9 +234,48 @@ class ViTTrainer(EpochTrainer):
         """timm's keys in timm's shapes (the patch-embedding weight 4-D), on the CPU."""
         return {k: self._param(k).detach().cpu().clone() for k in self.vit.p}
 
-    def fit(self, train_loader, valid_loader, epochs: int, out_dir: str, dataset: str) -> dict:
-        """mapping/train_transformer.py:104-172 (EpochTrainer._fit), saving checkpoint_path(out_dir, dataset)."""
-        return self._fit(train_loader, valid_loader, epochs, checkpoint_path(out_dir, dataset), f"Model vit on {dataset}")
+    # ---- the whole training state, for snapshots (snapshot.py) ---------------------------------------------------------------------
+    def _meta(self) -> dict:
+        vit, p = self.vit, self.vit.p
+        return dict({"format": snapshot.FORMAT, "kind": "vit", "embed_dim": vit.embed_dim, "depth": vit.depth, "patch": vit.patch,
+                     "in_chans": vit.in_chans, "tokens": p["pos_embed"].shape[1], "num_classes": p["head.weight"].shape[0]}, **self.run_meta)
+
+    def training_state(self) -> dict:
+        """{'meta', 'p' (the fp32 masters, timm's keys and shapes), 'm', 'v' (AdamW's moments under the same keys), 't', 'epoch'} on the
+        CPU, one tensor copied out at a time.  The frag32b3 images are not in it: they are a function of the masters."""
+        state = {"meta": self._meta(), "p": {k: self._param(k).detach().cpu() for k in self.vit.p}}
+        for which, src in (("m", self.m), ("v", self.v)):
+            state[which] = {k: src[k].detach().cpu() for k in self.vit.p}
+        state.update(t=int(self.t), epoch=int(self.epoch))
+        return state
+
+    def load_training_state(self, state: dict) -> None:
+        """training_state() of a run with this run's meta (snapshot.check_meta: a ValueError names the field that differs), copied into
+        the masters and moments in place after every shape has been checked; the frag32b3 images and their transposes are then rewritten
+        from the masters as at the end of a step (_refresh_images)."""
+        snapshot.check_meta(state.get("meta"), self._meta())
+        for which in ("p", "m", "v"):
+            for k in self.vit.p:
+                if k not in state[which] or tuple(state[which][k].shape) != tuple(self._param(k).shape):
+                    raise ValueError(f"{which}['{k}'] is missing or has another shape than {tuple(self._param(k).shape)}")
+        for k in self.vit.p:
+            self._param(k).copy_(state["p"][k])
+            self.m[k].copy_(state["m"][k])
+            self.v[k].copy_(state["v"][k])
+        self._refresh_images()
+        self.t, self.epoch = int(state["t"]), int(state["epoch"])
+
+    def fit(self, train_loader, valid_loader, epochs: int, out_dir: str, dataset: str, snapshot_path: Optional[str] = None,
+            snapshot_epochs: int = 0, resume: bool = False) -> dict:
+        """mapping/train_transformer.py:104-172 (EpochTrainer._fit), saving checkpoint_path(out_dir, dataset).  snapshot_epochs N: the
+        whole training state goes to snapshot_path (default: that path with the extension .ckpt) every N epochs and after the last;
+        resume: the run continues from that file."""
+        path = checkpoint_path(out_dir, dataset)
+        if snapshot_path is None and (snapshot_epochs or resume):
+            snapshot_path = path[:-4] + ".ckpt"
+        self.run_meta = dict(self.run_meta, dataset=dataset)
+        return self._fit(train_loader, valid_loader, epochs, path, f"Model vit on {dataset}", snapshot_path=snapshot_path,
+                         snapshot_epochs=snapshot_epochs, resume=resume)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -251,6 +292,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--epochs", type=int, default=None, help="default: per dataset (DATASET_DEFAULTS)")
     ap.add_argument("--batch_size", type=int, default=None, help="training batch; default: per dataset (DATASET_DEFAULTS)")
     add_cache_flags(ap)
+    add_snapshot_flags(ap, f"<out>/{SAVE_MODEL_NAME}_<Dataset>.ckpt")
     return ap
 
 
@@ -270,7 +312,7 @@ def main(argv=None) -> dict:
     trainer = ViTTrainer(sd, num_classes=s["num_classes"], num_heads=heads, lr=s["lr"], weight_decay=s["weight_decay"],
                          step_size=s["step_size"], gamma=s["gamma"], seed=s["seed"])
     train_loader, valid_loader = make_loaders(args.root_dir, args.dataset, args.preprocess, s["batch_size"], s["seed"], **cache_settings(args))
-    return trainer.fit(train_loader, valid_loader, s["epochs"], args.out, args.dataset)
+    return trainer.fit(train_loader, valid_loader, s["epochs"], args.out, args.dataset, **snapshot_settings(args))
 
 
 if __name__ == "__main__":
