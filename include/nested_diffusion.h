@@ -144,6 +144,31 @@ int nd_sample(nd_handle h, int member0, int n_members, const float *yhat_dev, co
               const float *noise_dev, float *y0_out_dev, float *seq_out_dev, int B, int mc, int T,
               int use_graph, void *stream);
 
+/* SAMPLER PLAN: fewer reverse steps from the schedule a member was trained on (not a reference mode: the reference declares --skip_type,
+ * --eta and --sample_type and never reads them).  With u = y - y_T_mean the forward process is plain DDPM in u, so any increasing
+ * subsequence 0 <= tau_0 < .. < tau_{S-1} <= n_steps - 1 is itself a chain.  With abar_t = 1 - one_minus_alphas_bar_sqrt[t]^2, the step
+ * from t = tau_j to r = tau_{j-1} (j >= 1) with eps = eps_theta(x, y, tau_j, yhat) and a draw z is
+ *     sigma = eta sqrt((1 - abar_r) / (1 - abar_t)) sqrt(1 - abar_t / abar_r)                    0 <= eta <= 1
+ *     cy = sqrt(abar_r / abar_t), cm = 1 - cy, ce = sqrt(1 - abar_r - sigma^2) - cy sqrt(1 - abar_t), cz = sigma
+ *     y_r = fmaf(cz, z, fmaf(ce, eps, fmaf(cm, y_T_mean, cy * y)))                              (fp32, no contraction)
+ * and the last one (row 0: p_sample_t_1to0 at tau_0) has cy = 1 / sqrt(abar), cm = -(1 - sqrt(abar)) / sqrt(abar), ce = -sqrt(1 - abar) /
+ * sqrt(abar), cz = 0.  The caller forms the S x 4 coefficients in double and rounds once (diffusion_utils.sampler_plan).
+ *   nd_set_sampler    timesteps_host [S] and coef_host [S][4] = (cy, cm, ce, cz) are HOST arrays, free again when the call returns.
+ *                     The handle keeps tau on the host (baked into kernel arguments) and the coefficients in a device buffer of its own:
+ *                     nd_workspace_bytes does not change.  S = 0 clears the plan (the pointers are not read).  Drops the recorded graphs.
+ *                     Refused (ND_ERR_ARG) before anything is allocated or copied: "handle is NULL", "S=.. outside [0,n_steps]",
+ *                     "timesteps_host / coef_host is NULL", "timesteps[j]=.. outside [0,n_steps)", "timesteps must be strictly
+ *                     increasing", "coefficient [j][q] is not finite".
+ *   nd_sampler_steps  S of the plan that is set, 0 for none.
+ * While a plan is set nd_sample and nd_predict_batch run its S steps: they take T == S and refuse any other T without writing anything
+ * (ND_ERR_STATE, "sampler plan holds S=.. steps, the call asks T=.. (nd_set_sampler)"); noise stays [n_members, T, M, C] (index 0 the
+ * initial draw, index i the draw of step i), seq_out [n_members, T+1, M, C], and the library's own noise is keyed on the call's shape as
+ * before.  Step i evaluates eps at embedding row tau_{S-1-i}; its head applies coefficient row S-i, the final kernel row 0.  The
+ * per-step loop form runs (the one-launch form knows consecutive timesteps only; nd_loop_form returns 0).  nd_eps_theta and nd_p_sample
+ * do not look at the plan.  The kernels of a plan are instantiations of their own: a handle without one launches what it always did. */
+int nd_set_sampler(nd_handle h, const int32_t *timesteps_host, const float *coef_host, int S, void *stream);
+int nd_sampler_steps(nd_handle h);
+
 /* Kernel-duration probes for the roofline report: when enabled, up to 8 PAIRS of consecutive denoising steps (i, i+1) of every
  * nd_sample / nd_predict_batch graph (or eager loop) get hipEvent record nodes on the launch stream: before the head of step i, after
  * it, after the two ConditionalLinear launches of step i, and after those of step i+1.  nd_profile_read (after the stream is
@@ -862,6 +887,12 @@ int nd_cond_act_bwd(const float *dh_dev, const float *h_dev, const float *a_t_de
                     int M, int N, int B, void *stream);
 int nd_reverse_step(int mode, const float *y_dev, int ldy, const float *ymean_dev, const float *eps_dev, const float *z_dev, float *out_dev,
                     int ldo, int M, int B, int C, float alpha_t, float s_t, float s_tm1, void *stream);
+/* nd_reverse_step's layouts for one step of a sampler plan (nd_set_sampler: strided timesteps, generalized eta update), the taped
+ * forward of the ensemble gradient:  out[r][c] = fmaf(cz, z, fmaf(ce, eps, fmaf(cm, ymean[r % B], cy * y)))  -- the device function the
+ * sampler's coefficient kernels call, so the bits are theirs.  z_dev may be NULL when cz == 0 (the plan's row 0, or eta = 0): 0 is used
+ * for the draw.  Non-finite coefficients are refused.  nd_reverse_step_bwd with the same (cy, cm, ce) is its backward. */
+int nd_reverse_step_coef(const float *y_dev, int ldy, const float *ymean_dev, const float *eps_dev, const float *z_dev, float *out_dev,
+                         int ldo, int M, int B, int C, float cy, float cm, float ce, float cz, void *stream);
 int nd_reverse_step_bwd(const float *g_dev, int ldg, float cy, float cm, float ce, float *deps_dev, float *dyadd_dev, int lda,
                         float *dymean_dev, int M, int B, int C, void *stream);
 int nd_aggregate_xent_bwd(const float *samples_dev, const int64_t *labels_dev, float *P_dev, float *loss_dev, float *dsamples_dev, int S,

@@ -112,6 +112,8 @@ SIGNATURES = {
     "nd_eps_theta": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "nd_p_sample": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "nd_sample": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "nd_set_sampler": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), _i, _vp]),
+    "nd_sampler_steps": (_i, [_vp]),
     "nd_set_profiling": (_i, [_vp, _i]),
     "nd_set_input_flag": (_i, [_vp, _vp]),
     "nd_set_loop_form": (_i, [_vp, _i, C.c_float]),
@@ -216,6 +218,7 @@ SIGNATURES = {
     "nd_cond_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "nd_cond_act_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nd_reverse_step": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "nd_reverse_step_coef": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp]),
     "nd_reverse_step_bwd": (_i, [_vp, _i, _f, _f, _f, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "nd_aggregate_xent_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "nd_softmax_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

@@ -3,6 +3,7 @@
 //   k_cond_mul              y1 = s1 (.) xe[r % B]: the product of latent_model.py:177, kept apart from nd_linear's epilogue so that s1 stays
 //   k_cond_act_bwd          the eval-mode backward of one ConditionalLinear + BatchNorm + softplus block, from the taped softplus OUTPUT
 //   k_reverse_step          y_T = z + y_T_mean, p_sample, p_sample_t_1to0 on [M, C] (nd_step.hpp's nd_posterior / nd_y0_reparam, shared)
+//   k_reverse_step_coef     one step of a sampler plan (strided / eta) on [M, C]: nd_step.hpp's nd_coef_update, shared with the sampler
 //   k_reverse_step_bwd      the backward of one such step: it is affine, three host-formed coefficients
 //   k_aggregate_xent_bwd    -log(mean_s softmax(-(y0_s - 1)^2 / tau))[label] and its gradient at every sample
 //   k_softmax_bwd           dlogits = p (.) (dp - sum_c dp p)
@@ -15,6 +16,8 @@
 // instantiated per class count (1 .. 16) so that the per-class arrays are registers, not scratch.
 #include "nd_host.hpp"
 #include "nd_step.hpp"
+
+#include <cmath>
 
 namespace {
 
@@ -70,6 +73,20 @@ __global__ __launch_bounds__(256) void k_reverse_step(int mode, const float* __r
     } else if (c < 2 * C) {
         v = ymean[b * C + (c - C)];
     }
+    out[e] = v;
+}
+
+// k_reverse_step's layouts with the update in coefficient form (a sampler plan's step: nd_step.hpp's nd_coef_update, the device function
+// of the sampler's own coefficient kernels); z null: no draw is read (the step's cz is 0: the last step, or eta = 0).
+__global__ __launch_bounds__(256) void k_reverse_step_coef(const float* __restrict__ y, int ldy, const float* __restrict__ ymean,
+                                                           const float* __restrict__ eps, const float* __restrict__ z, float* __restrict__ out, int ldo,
+                                                           int M, int B, int C, float cy, float cm, float ce, float cz) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= M * ldo) return;
+    const int r = e / ldo, c = e - r * ldo, b = r % B;
+    float v = 0.f;
+    if (c < C) v = nd_coef_update(y[r * ldy + c], ymean[b * C + c], eps[r * C + c], z ? z[r * C + c] : 0.f, cy, cm, ce, cz);
+    else if (c < 2 * C) v = ymean[b * C + (c - C)];
     out[e] = v;
 }
 
@@ -222,6 +239,24 @@ extern "C" int nd_reverse_step(int mode, const float* y, int ldy, const float* y
     if (out == y || out == ymean || out == eps || out == z) return nd_set_err(ND_ERR_ARG, "reverse_step: out aliases an input");
     hipLaunchKernelGGL(k_reverse_step, dim3((unsigned)((M * ldo + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mode, y, ldy, ymean, eps, z, out,
                        ldo, M, B, C, alpha_t, s_t, s_tm1);
+    HIP_CHECK(hipGetLastError());
+    return ND_OK;
+}
+
+extern "C" int nd_reverse_step_coef(const float* y, int ldy, const float* ymean, const float* eps, const float* z, float* out, int ldo, int M, int B,
+                                    int C, float cy, float cm, float ce, float cz, void* stream) {
+    if (!y || !ymean || !eps || !out) return nd_set_err(ND_ERR_ARG, "reverse_step_coef: NULL tensor");
+    if (!std::isfinite(cy) || !std::isfinite(cm) || !std::isfinite(ce) || !std::isfinite(cz))
+        return nd_set_err(ND_ERR_ARG, "reverse_step_coef: a coefficient is not finite");
+    if (!z && cz != 0.f) return nd_set_err(ND_ERR_ARG, "reverse_step_coef: cz=%g needs the draw z", (double)cz);
+    if (M < 1 || B < 1 || M % B || M > ND_LINEAR_BWD_MAX_M * 64 || C < 1 || C > ND_MAX_C)
+        return nd_set_err(ND_ERR_ARG, "reverse_step_coef needs 1 <= M <= %d, B >= 1, M %% B == 0 and 1 <= C <= %d (M=%d, B=%d, C=%d)",
+                          ND_LINEAR_BWD_MAX_M * 64, ND_MAX_C, M, B, C);
+    if (ldo != C && (ldo < 2 * C || ldo > 64)) return nd_set_err(ND_ERR_ARG, "reverse_step_coef: ldo must be C or in [2C, 64] (ldo=%d, C=%d)", ldo, C);
+    if (ldy < C || ldy > 64) return nd_set_err(ND_ERR_ARG, "reverse_step_coef: ldy must lie in [C, 64] (ldy=%d, C=%d)", ldy, C);
+    if (out == y || out == ymean || out == eps || out == z) return nd_set_err(ND_ERR_ARG, "reverse_step_coef: out aliases an input");
+    hipLaunchKernelGGL(k_reverse_step_coef, dim3((unsigned)((M * ldo + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, ldy, ymean, eps, z, out,
+                       ldo, M, B, C, cy, cm, ce, cz);
     HIP_CHECK(hipGetLastError());
     return ND_OK;
 }

@@ -7,6 +7,7 @@
 #include "nd_b9.hpp"
 #include "nd_persist.hpp"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -149,6 +150,7 @@ extern "C" int nd_destroy(nd_handle h) {
     nd_drop_graphs(h);
     for (hipEvent_t e : h->probe_events) (void)hipEventDestroy(e);
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
+    if (h->plan_coef) (void)hipFree(h->plan_coef);
     delete h;
     return ND_OK;
 }
@@ -210,6 +212,42 @@ extern "C" int nd_set_schedule(nd_handle h, const float* alphas_dev, const float
     h->sched_T = T;
     return ND_OK;
 }
+
+extern "C" int nd_set_sampler(nd_handle h, const int32_t* timesteps_host, const float* coef_host, int S, void* stream) {
+    // every argument first: nothing is allocated, copied or dropped by a refused call
+    if (!h) return nd_set_err(ND_ERR_ARG, "set_sampler: handle is NULL");
+    if (S < 0 || S > h->cfg.n_steps) return nd_set_err(ND_ERR_ARG, "set_sampler: S=%d outside [0,%d]", S, h->cfg.n_steps);
+    if (S > 0 && (!timesteps_host || !coef_host)) return nd_set_err(ND_ERR_ARG, "set_sampler: timesteps_host / coef_host is NULL");
+    for (int j = 0; j < S; ++j) {
+        const int t = timesteps_host[j];
+        if (t < 0 || t >= h->cfg.n_steps) return nd_set_err(ND_ERR_ARG, "set_sampler: timesteps[%d]=%d outside [0,%d)", j, t, h->cfg.n_steps);
+        if (j > 0 && t <= timesteps_host[j - 1])
+            return nd_set_err(ND_ERR_ARG, "set_sampler: timesteps must be strictly increasing (timesteps[%d]=%d after %d)", j, t, timesteps_host[j - 1]);
+    }
+    for (int j = 0; j < 4 * S; ++j)
+        if (!std::isfinite(coef_host[j])) return nd_set_err(ND_ERR_ARG, "set_sampler: coefficient [%d][%d] is not finite", j / 4, j % 4);
+    if (S == 0) {
+        h->plan_tau.clear();
+        nd_drop_graphs(h);
+        return ND_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (h->plan_cap < S) {       // set time only: the buffer grows to the longest plan the handle has seen
+        HIP_CHECK(hipDeviceSynchronize());       // no loop of an earlier plan may still be reading the buffer that is released
+        if (h->plan_coef) HIP_CHECK(hipFree(h->plan_coef));
+        h->plan_coef = nullptr; h->plan_cap = 0; h->plan_tau.clear();
+        HIP_CHECK(hipMalloc((void**)&h->plan_coef, sizeof(float) * 4 * (size_t)S));
+        h->plan_cap = S;
+    }
+    // behind everything enqueued on `stream` so far; the host waits, so the caller's arrays are free when this returns
+    HIP_CHECK(hipMemcpyAsync(h->plan_coef, coef_host, sizeof(float) * 4 * (size_t)S, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    h->plan_tau.assign(timesteps_host, timesteps_host + S);
+    nd_drop_graphs(h);
+    return ND_OK;
+}
+
+extern "C" int nd_sampler_steps(nd_handle h) { return h ? (int)h->plan_tau.size() : 0; }
 
 extern "C" int nd_load_member(nd_handle h, int k, const nd_member_weights* w, void* stream) {
     if (!h || !h->ws) return nd_set_err(ND_ERR_STATE, "workspace not bound");

@@ -71,6 +71,9 @@ struct nd_handle_s {
     float* noise_ws = nullptr;             // [K][T][max_rows][C] draws of the in-library noise (noise_dev == NULL)
     float* logits_ws = nullptr;            // [K][max_batch][C] guiding-prediction logits of nd_predict_batch
     int sched_T = 0;
+    std::vector<int> plan_tau;             // sampler plan (nd_set_sampler): the S timesteps tau_0 < .. < tau_{S-1}, baked into kernel arguments; empty: none
+    float* plan_coef = nullptr;            // ... and its [S][4] coefficients (cy, cm, ce, cz) in a device buffer of the handle's own (not the workspace)
+    int plan_cap = 0;                      // rows that buffer holds
     int NT = 0, S0 = 0;
     bool enc_splitk = false;
     int half = 0;                          // cfg.operand_dtype == ND_DTYPE_F16

@@ -143,6 +143,13 @@ static int check_rows(nd_handle_s* h, int B, int mc, int T, bool need_encoded = 
     return ND_OK;
 }
 
+// With a sampler plan set (nd_set_sampler) the loop runs the plan's S steps: the entry points that run the loop take T == S only.
+static int check_plan(const nd_handle_s* h, int T) {
+    const int S = (int)h->plan_tau.size();
+    if (S && T != S) return nd_set_err(ND_ERR_STATE, "sampler plan holds S=%d steps, the call asks T=%d (nd_set_sampler)", S, T);
+    return ND_OK;
+}
+
 // Which operand layout emit_loop picks for the step blocks of a launch over nm members at M rows (its `b9`): the frag32b3 images on the
 // bf16 matrix pipe above 128 rows where the handle holds them and the descriptors travel by value.  Recorded per member at every entry
 // point that runs the loop (graph replays included: the choice is a function of the call's shape) so that nd_member_buffer reads the
@@ -288,9 +295,13 @@ static hipError_t emit_loop(nd_handle_s* h, Emitter& em, int m0, int nm, StepIO 
         i2.d[g] = h->descs_host[(size_t)L_LIN2 * K + m0 + g];
         i3.d[g] = h->descs_host[(size_t)L_LIN3 * K + m0 + g];
     }
-    // ONE launch for the whole loop where the plan allows (csrc/nd_persist.hip)
+    // a sampler plan: step i evaluates eps at timestep tau[S-1-i] (the embedding row of the head and of both blocks) and its head applies
+    // coefficient row S-i to the state of step i-1; the final kernel applies row 0.  T == S (check_plan).
+    const int* tau = h->plan_tau.empty() ? nullptr : h->plan_tau.data();
+    if (tau) io.alphas = h->plan_coef;
+    // ONE launch for the whole loop where the plan allows (csrc/nd_persist.hip; it knows consecutive timesteps only)
     h->persist_last = false;
-    if (h->persist_mode && inl) {
+    if (h->persist_mode && inl && !tau) {
         const PersistPlan pp = nd_persist_plan(F, M, nm, C, h->half);
         if (pp.ok) {
             if (pp.err != hipSuccess) return pp.err;
@@ -337,7 +348,7 @@ static hipError_t emit_loop(nd_handle_s* h, Emitter& em, int m0, int nm, StepIO 
     // ... and the head in its many-rows form (16 rows per workgroup, whole operand planes per store; same bits)
     const bool rows_head = b9 && NT <= 64 && !getenv("ND_HEAD_PER_ROW");
     const dim3 ghead_rows((F + ND_HEAD_ROWS_COLS - 1) / ND_HEAD_ROWS_COLS, (M + 15) / 16, nm);
-    void* const head_fn = nd_step_head_kernel(C, rows_head);
+    void* const head_fn = nd_step_head_kernel(C, rows_head, tau != nullptr);
     // probes: up to 8 PAIRS of steps (i, i+1) spread over the loop (never step 0: its head is the cheap INIT form).  Records
     // around head(i), around the two blocks of step i, and behind the blocks of step i+1: the third interval is one whole unrecorded
     // step, so  (whole step) - (two blocks) = the head alone, and what a record node adds to an interval follows from the head's
@@ -350,8 +361,8 @@ static hipError_t emit_loop(nd_handle_s* h, Emitter& em, int m0, int nm, StepIO 
     int probed = 0;
     HeadArgs ha{mi, mdev, io, 0, 0, 0, 0, B, M, maxM, F, NT, T};
     for (int i = 0; i < T; ++i) {
-        int t = T - 1 - i;
-        ha.mode = (i == 0) ? ND_HEAD_INIT : ND_HEAD_UPDATE; ha.i_step = i; ha.t_prev = t + 1; ha.t = t;
+        int t = tau ? tau[T - 1 - i] : T - 1 - i;
+        ha.mode = (i == 0) ? ND_HEAD_INIT : ND_HEAD_UPDATE; ha.i_step = i; ha.t_prev = tau ? T - i : t + 1; ha.t = t;
         const bool probe = want > 0 && i >= 1 && i + 1 < T && !pending_end && probed < want && ((i - 1) % stride) == (stride - 1) / 2;
         hipEvent_t* ev = probe ? &h->probe_events[4 * probed] : nullptr;
         hipEvent_t end_of_pair = pending_end;      // this step closes the pair opened by the previous one
@@ -385,7 +396,7 @@ static hipError_t emit_loop(nd_handle_s* h, Emitter& em, int m0, int nm, StepIO 
     }
     h->probe_steps = probed;
     FinalArgs fa{mi, mdev, io, 0, (T - 1) & 1, B, M, maxM, NT, T, nullptr, 0};
-    em.emit(nd_step_final_kernel(C), dim3(M, 1, nm), dim3(64), fa.ptrs());
+    em.emit(nd_step_final_kernel(C, tau != nullptr), dim3(M, 1, nm), dim3(64), fa.ptrs());
     return em.err;
 }
 
@@ -428,6 +439,7 @@ extern "C" int nd_sample(nd_handle h, int m0, int nm, const float* yhat_dev, con
     if (rc != ND_OK) return rc;
     if (!yhat_dev || !ymean_dev || !y0_out_dev) return nd_set_err(ND_ERR_ARG, "NULL tensor");
     rc = check_rows(h, B, mc, T);
+    if (rc == ND_OK) rc = check_plan(h, T);
     if (rc != ND_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int C = h->cfg.y_dim, M = B * mc;
@@ -508,6 +520,7 @@ extern "C" int nd_predict_batch(nd_handle h, nd_cond c, const float* images_dev,
     if (rc != ND_OK) return rc;
     if (B < 1 || B > g.max_batch || B > cc->max_batch) return nd_set_err(ND_ERR_ARG, "B=%d outside [1,%d]", B, g.max_batch < cc->max_batch ? g.max_batch : cc->max_batch);
     rc = check_rows(h, B, mc, T, false);      // the batch encodes for itself
+    if (rc == ND_OK) rc = check_plan(h, T);
     if (rc != ND_OK) return rc;
     if (!(temperature > 0.f)) return nd_set_err(ND_ERR_ARG, "temperature must be > 0");
     hipStream_t st = (hipStream_t)stream;

@@ -44,7 +44,8 @@ __device__ __forceinline__ void nd_reduce_eps(const float* __restrict__ epart, i
 // (latent_model.py:173-177).  Grid (ceil(F/1024), M, members), 256 threads, 4 columns per thread.
 // Every thread computes y_t redundantly (C values), so nothing crosses threads after the reduce; the
 // table / xe / lin1 loads are issued before the reduction so their latency overlaps it.
-template <int C>
+// COEF (a sampler plan, nd_set_sampler): the update is nd_coef_update with row t_prev of the plan's table (io.alphas), see nd_step.hpp.
+template <int C, bool COEF = false>
 __global__ __launch_bounds__(256) void k_step_head(MemberInline mi, const MemberDev* __restrict__ members, StepIO io, int mode, int i_step,
                                                    int t_prev, int t, int B, int M, int maxM, int F, int NT, int T) {
     typedef const __attribute__((address_space(4))) char* nd_cbytes;           // scalar loads from either source (see k_skinny)
@@ -85,8 +86,14 @@ __global__ __launch_bounds__(256) void k_step_head(MemberInline mi, const Member
             zz[c] = ND_GC(io.noise)[z * io.noise_ms + ((size_t)i_step * M + m) * C + c];
         }
     }
+    float cf[4] = {0.f, 0.f, 0.f, 0.f};
     if (mode == ND_HEAD_UPDATE) {
-        al = ND_GC(io.alphas)[t_prev]; s_t = ND_GC(io.omabs)[t_prev]; s_tm1 = ND_GC(io.omabs)[t_prev - 1];
+        if constexpr (COEF) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cf[q] = ND_GC(io.alphas)[4 * t_prev + q];
+        } else {
+            al = ND_GC(io.alphas)[t_prev]; s_t = ND_GC(io.omabs)[t_prev]; s_tm1 = ND_GC(io.omabs)[t_prev - 1];
+        }
 #pragma unroll
         for (int c = 0; c < C; ++c) yo[c] = yold[c];
         nd_reduce_eps<256, C>(mb.epart, NT, m, red, eps);
@@ -94,7 +101,9 @@ __global__ __launch_bounds__(256) void k_step_head(MemberInline mi, const Member
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         if (mode == ND_HEAD_INIT) yv[c] = zz[c] + ym[c];
-        else if (mode == ND_HEAD_UPDATE) yv[c] = nd_posterior(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], al, s_t, s_tm1);
+        else if (mode == ND_HEAD_UPDATE)
+            yv[c] = COEF ? nd_coef_update(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], cf[0], cf[1], cf[2], cf[3])
+                         : nd_posterior(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], al, s_t, s_tm1);
         else yv[c] = ND_GC(io.y_in)[z * io.yin_ms + (size_t)m * C + c];
         if (tid == 0 && blockIdx.x == 0) {
             ynew[c] = yv[c];
@@ -123,7 +132,7 @@ __global__ __launch_bounds__(256) void k_step_head(MemberInline mi, const Member
 // computes the 8 consecutive k of one row that are its 16 bytes of an MFMA operand plane, so a wave writes whole 1 KiB planes of
 // the image (k_step_head's 8-byte pieces land 256 bytes apart).
 // Grid (ceil(F/ND_HEAD_ROWS_COLS), ceil(M/16), members), 256 threads; F % 32 == 0, NT <= 64.
-template <int C>
+template <int C, bool COEF = false>
 __global__ __launch_bounds__(256) void k_step_head_rows(MemberInline mi, const MemberDev* __restrict__ members, StepIO io, int mode,
                                                         int i_step, int t_prev, int t, int B, int M, int maxM, int F, int NT, int T) {
     typedef const __attribute__((address_space(4))) char* nd_cbytes;
@@ -151,8 +160,14 @@ __global__ __launch_bounds__(256) void k_step_head_rows(MemberInline mi, const M
                 zz[c] = ND_GC(io.noise)[z * io.noise_ms + ((size_t)i_step * M + m) * C + c];
             }
         }
+        float cf[4] = {0.f, 0.f, 0.f, 0.f};
         if (mode == ND_HEAD_UPDATE) {
-            al = ND_GC(io.alphas)[t_prev]; s_t = ND_GC(io.omabs)[t_prev]; s_tm1 = ND_GC(io.omabs)[t_prev - 1];
+            if constexpr (COEF) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) cf[q] = ND_GC(io.alphas)[4 * t_prev + q];
+            } else {
+                al = ND_GC(io.alphas)[t_prev]; s_t = ND_GC(io.omabs)[t_prev]; s_tm1 = ND_GC(io.omabs)[t_prev - 1];
+            }
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 yo[c] = yold[c];
@@ -178,7 +193,9 @@ __global__ __launch_bounds__(256) void k_step_head_rows(MemberInline mi, const M
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             if (mode == ND_HEAD_INIT) yv[c] = zz[c] + ym[c];
-            else if (mode == ND_HEAD_UPDATE) yv[c] = nd_posterior(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], al, s_t, s_tm1);
+            else if (mode == ND_HEAD_UPDATE)
+                yv[c] = COEF ? nd_coef_update(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], cf[0], cf[1], cf[2], cf[3])
+                             : nd_posterior(yo[c], ym[c], eps[c] + ND_GC(mb.lin4_b)[c], zz[c], al, s_t, s_tm1);
             else yv[c] = ND_GC(io.y_in)[z * io.yin_ms + (size_t)m * C + c];
             if (j == 0) {
                 ys[r][c] = yv[c]; yhs[r][c] = yh[c];
@@ -233,7 +250,8 @@ __global__ __launch_bounds__(256) void k_step_head_rows(MemberInline mi, const M
 // eps_theta entry point.  Grid (M, 1, members), 64 threads.
 // eps_only: 0 = y_0 of the loop, 1 = eps output, 2 = one p_sample step from io.y_in with the draw in
 // io.noise (t = par_cur), 3 = p_sample_t_1to0 from io.y_in.
-template <int C>
+// COEF: y_0 of the loop (eps_only 0) is nd_coef_update with row 0 of the plan's table (io.alphas): its cz is 0 and no draw is read.
+template <int C, bool COEF = false>
 __global__ __launch_bounds__(64) void k_step_final(MemberInline mi, const MemberDev* __restrict__ members, StepIO io, int eps_only, int par_cur,
                                                    int B, int M, int maxM, int NT, int T, float* eps_out, size_t eps_ms) {
     typedef const __attribute__((address_space(4))) char* nd_cbytes;           // scalar loads from either source (see k_skinny)
@@ -259,7 +277,8 @@ __global__ __launch_bounds__(64) void k_step_final(MemberInline mi, const Member
             } else {
                 const float y = mb.ybuf[((size_t)par_cur * maxM + m) * C + c];
                 const float ymean = io.ymean[z * io.ymean_ms + (size_t)b * C + c];
-                const float y0 = nd_y0_reparam(y, ymean, eps, io.omabs[0]);
+                const float y0 = COEF ? nd_coef_update(y, ymean, eps, 0.f, io.alphas[0], io.alphas[1], io.alphas[2], io.alphas[3])
+                                      : nd_y0_reparam(y, ymean, eps, io.omabs[0]);
                 io.y0_out[z * io.y0_ms + (size_t)m * C + c] = y0;
                 if (io.seq_out) io.seq_out[z * io.seq_ms + ((size_t)T * M + m) * C + c] = y0;
             }
@@ -272,5 +291,12 @@ __global__ __launch_bounds__(64) void k_step_final(MemberInline mi, const Member
     ((C) == 1 ? (void*)K<1> : (C) == 2 ? (void*)K<2> : (C) == 3 ? (void*)K<3> : (C) == 4 ? (void*)K<4> : (C) == 5 ? (void*)K<5> \
    : (C) == 6 ? (void*)K<6> : (C) == 7 ? (void*)K<7> : (void*)K<8>)
 
-void* nd_step_head_kernel(int C, bool rows) { return rows ? ND_KERNEL_BY_C(k_step_head_rows, C) : ND_KERNEL_BY_C(k_step_head, C); }
-void* nd_step_final_kernel(int C) { return ND_KERNEL_BY_C(k_step_final, C); }
+#define ND_COEF_KERNEL_BY_C(K, C)                                                                                                \
+    ((C) == 1 ? (void*)K<1, true> : (C) == 2 ? (void*)K<2, true> : (C) == 3 ? (void*)K<3, true> : (C) == 4 ? (void*)K<4, true>       \
+   : (C) == 5 ? (void*)K<5, true> : (C) == 6 ? (void*)K<6, true> : (C) == 7 ? (void*)K<7, true> : (void*)K<8, true>)
+
+void* nd_step_head_kernel(int C, bool rows, bool coef) {
+    if (coef) return rows ? ND_COEF_KERNEL_BY_C(k_step_head_rows, C) : ND_COEF_KERNEL_BY_C(k_step_head, C);
+    return rows ? ND_KERNEL_BY_C(k_step_head_rows, C) : ND_KERNEL_BY_C(k_step_head, C);
+}
+void* nd_step_final_kernel(int C, bool coef) { return coef ? ND_COEF_KERNEL_BY_C(k_step_final, C) : ND_KERNEL_BY_C(k_step_final, C); }

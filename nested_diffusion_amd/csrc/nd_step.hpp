@@ -41,7 +41,7 @@ struct StepIO {             // per-launch tensors with a member-major leading st
     float* y0_out;      size_t y0_ms;      // [nm][M][C]
     float* seq_out;     size_t seq_ms;     // [nm][T+1][M][C] or null
     const float* y_in;  size_t yin_ms;     // [nm][M][C] (eps_theta entry point only)
-    const float* alphas; const float* omabs;
+    const float* alphas; const float* omabs;               // the coefficient-form kernels (below): alphas = the plan's [S][4] table
 };
 
 #define ND_HEAD_INIT 0    // y = noise[0] + y_T_mean                       (diffusion_utils.py:139-140)
@@ -55,8 +55,11 @@ struct StepIO {             // per-launch tensors with a member-major leading st
 //       256 threads; grid (ceil(F/1024), M, members), rows: (ceil(F/ND_HEAD_ROWS_COLS), ceil(M/16), members)
 //   final: (MemberInline mi, const MemberDev* members, StepIO io, int eps_only, int par_cur, int B, int M, int maxM, int NT, int T, float* eps_out, size_t eps_ms)
 //       64 threads; grid (M, 1, members)
-void* nd_step_head_kernel(int C, bool rows);
-void* nd_step_final_kernel(int C);
+// coef: the instantiations of a sampler plan (nd_set_sampler).  Same argument lists; io.alphas then points at the plan's coefficient
+// table [S][4] = (cy, cm, ce, cz), t_prev (head) is the coefficient ROW of the update and t the embedding row; the final kernel's
+// loop form (eps_only 0) reads row 0.  The default instantiations are the ones every call without a plan launches.
+void* nd_step_head_kernel(int C, bool rows, bool coef = false);
+void* nd_step_final_kernel(int C, bool coef = false);
 
 // diffusion_utils.py:68-92 in the reference's operation order, fp32, no FMA contraction, so the
 // posterior is bit-identical to the CPU path for identical eps.
@@ -75,6 +78,15 @@ __device__ __forceinline__ float nd_posterior(float y, float ymean, float eps, f
     const float mean = g0 * y0r + g1 * y + g2 * ymean;
     const float bh = stm2 / st2 * (1.0f - alpha_t);
     return mean + sqrtf(bh) * z;
+}
+
+// The reverse step in coefficient form (a sampler plan: any increasing subsequence of the schedule, generalized eta update; the host
+// forms cy, cm, ce, cz in double and rounds once): ONE pinned sequence of three FMAs on a rounded product, no contraction, shared by
+// both step heads, the final kernel and nd_reverse_step_coef, so that all of them return the same bits.
+__device__ __forceinline__ float nd_coef_update(float y, float ymean, float eps, float z, float cy, float cm, float ce, float cz) {
+#pragma clang fp contract(off)
+    const float p = cy * y;
+    return __builtin_fmaf(cz, z, __builtin_fmaf(ce, eps, __builtin_fmaf(cm, ymean, p)));
 }
 
 // diffusion_utils.py:99-111

@@ -165,6 +165,27 @@ class EnsembleEngine:
                                    self._stream()), "nd_p_sample")
         return out
 
+    def set_sampler(self, plan) -> None:
+        """Run sample() / predict_batch() over a sampler plan (nd_set_sampler): plan = diffusion_utils.sampler_plan(...) or any
+        (timesteps [S], coef [S, 4]) pair.  Until clear_sampler() both take T = S = sampler_steps() and nothing else; noise is
+        [.., S, M, C], a trajectory has S + 1 entries.  Not a reference mode.  None clears."""
+        if plan is None:
+            return self.clear_sampler()
+        tau = torch.as_tensor(plan[0]).detach().cpu().to(torch.int32).reshape(-1).contiguous()
+        coef = torch.as_tensor(plan[1]).detach().cpu().to(torch.float32).contiguous()
+        if tau.numel() < 1 or tuple(coef.shape) != (tau.numel(), 4):
+            raise ValueError(f"a sampler plan is (timesteps [S], coef [S, 4]) with S >= 1, got {tuple(tau.shape)} and {tuple(coef.shape)}")
+        check(self.lib.nd_set_sampler(self.h, C.cast(tau.data_ptr(), C.POINTER(C.c_int32)), C.cast(coef.data_ptr(), C.POINTER(C.c_float)),
+                                      tau.numel(), self._stream()), "nd_set_sampler")
+
+    def clear_sampler(self) -> None:
+        """Back to the full chain of the schedule (the default path, bit for bit)."""
+        check(self.lib.nd_set_sampler(self.h, None, None, 0, self._stream()), "nd_set_sampler")
+
+    def sampler_steps(self) -> int:
+        """S of the plan that is set, 0 for none (nd_sampler_steps)."""
+        return int(self.lib.nd_sampler_steps(self.h))
+
     def set_loop_form(self, one_launch: bool, skew_us: float = -1.0) -> None:
         """Form of the T-step loop (nd_set_loop_form): per-step kernel nodes of a hipGraph, or ONE launch per p_sample_loop where
         the shape allows (same bits; needs the device to itself while it runs).  skew_us < 0 keeps the current member skew."""
@@ -257,7 +278,7 @@ class EnsembleEngine:
         yhat, ymean: [n_members, B, C]; noise: [n_members, T, B*mc, C] in the reference's draw order, or None: the library draws
         it (Philox, see seed()).  Returns y_0 [n_members, B*mc, C] (or the whole trajectory [n_members, T+1, B*mc, C])."""
         n_members = self.K - member0 if n_members is None else n_members
-        T = self.T if T is None else T
+        T = (self.sampler_steps() or self.T) if T is None else T
         if yhat.dim() != 3 or yhat.shape[0] != n_members or yhat.shape[2] != self.C:
             raise ValueError(f"yhat must be [{n_members}, B, {self.C}], got {tuple(yhat.shape)}")
         B = yhat.shape[1]

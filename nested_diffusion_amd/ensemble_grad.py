@@ -34,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
-from .diffusion_utils import schedule_tables
+from .diffusion_utils import sampler_plan, schedule_tables, timestep_sequence
 from .latent_model import LIN1_K, check_member_dims, member_shapes, pad_lin1
 from .mapping import require_fp32_split
 from .ops import BN_EPS
@@ -115,14 +115,25 @@ class SamplerTape:
     forward(x_flat, yhat, noise) -> y0 [M, C], backward(dy0) -> (dx_flat [B, D], dyhat [B, C]).  The seven Linear weights are held as
     ops.PackedWeight images (lin1 padded to LIN1_K columns), BatchNorm, bias and the per-timestep gain folded into [T, F] tables once,
     here (torch arithmetic in double: load time).  y_T_mean and y_0_hat are the same tensor yhat.  Accepted shapes: D, H, F
-    positive multiples of 16, 1 <= C <= 8, T >= 1 (T = 1 is the p_sample_t_1to0-only chain)."""
+    positive multiples of 16, 1 <= C <= 8, T >= 1 (T = 1 is the p_sample_t_1to0-only chain).
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], alphas: torch.Tensor, one_minus_alphas_bar_sqrt: torch.Tensor, device="cuda"):
+    timesteps (default None: every timestep, the reference's chain): a sampler plan (diffusion_utils.sampler_plan(.., timesteps, eta)) --
+    the chain then has S = len(timesteps) steps, position j evaluating eps at timestep timesteps[j]; its forward goes through
+    ops.reverse_step_coef (the sampler's own device function), its backward uses (cy, cm, ce) of the same plan, noise is [S, M, C] and
+    the tape holds S steps."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], alphas: torch.Tensor, one_minus_alphas_bar_sqrt: torch.Tensor, device="cuda",
+                 timesteps: Optional[Sequence[int]] = None, eta: float = 1.0):
         self.C, self.D, self.H, self.F, T_emb = member_dims(state_dict)
         self.coef = reverse_step_coefficients(alphas, one_minus_alphas_bar_sqrt).tolist()
         self.T = len(self.coef)
         if self.T > T_emb:
             raise ValueError(f"the schedule has {self.T} timesteps, the embedding tables {T_emb}")
+        self.plan = None if timesteps is None else sampler_plan(one_minus_alphas_bar_sqrt, timesteps, eta)
+        if self.plan is not None:
+            self.coef = self.plan.coef.tolist()                                 # rows (cy, cm, ce, cz); the backward reads the first three
+        self.rows = list(range(self.T)) if self.plan is None else self.plan.timesteps.tolist()    # chain position j -> timestep
+        self.S = len(self.rows)
         self.alphas = alphas.detach().cpu().float().reshape(-1).tolist()
         self.omabs = one_minus_alphas_bar_sqrt.detach().cpu().float().reshape(-1).tolist()
         self.device = torch.device(device)
@@ -147,15 +158,16 @@ class SamplerTape:
         B = x_flat.shape[0]
         if tuple(yhat.shape) != (B, self.C):
             raise ValueError(f"yhat must be [{B}, {self.C}], got {tuple(yhat.shape)}")
-        if noise.dim() != 3 or noise.shape[0] != self.T or noise.shape[2] != self.C or noise.shape[1] < B or noise.shape[1] % B:
-            raise ValueError(f"noise must be [{self.T}, B * mc, {self.C}] with B = {B}, got {tuple(noise.shape)}")
+        if noise.dim() != 3 or noise.shape[0] != self.S or noise.shape[2] != self.C or noise.shape[1] < B or noise.shape[1] % B:
+            raise ValueError(f"noise must be [{self.S}, B * mc, {self.C}] with B = {B}, got {tuple(noise.shape)}")
         return B, noise.shape[1]
 
     def forward(self, x_flat: torch.Tensor, yhat: torch.Tensor, noise: torch.Tensor, record: bool = True) -> torch.Tensor:
         """y0 [M, C] of p_sample_loop (diffusion_utils.py:133-163) with noise [T, M, C] in the reference's draw order: row 0 the initial
-        draw, row i the draw of p_sample at t = T - i.  record=False keeps no tape (EnsembleTarget.forward)."""
+        draw, row i the draw of p_sample at t = T - i (with a plan: [S, M, C], row i the draw of the step that leaves chain position
+        S - i).  record=False keeps no tape (EnsembleTarget.forward)."""
         B, M = self._check(x_flat, yhat, noise)
-        w, a, c, T = self.w, self.a, self.c, self.T
+        w, a, c, T = self.w, self.a, self.c, self.S
         x_flat, yhat, noise = x_flat.contiguous(), yhat.contiguous(), noise.contiguous()
         e0 = ops.linear(x_flat, w["enc0"], c["enc0"][0], act="softplus", scale=a["enc0"][0])
         e1 = ops.linear(e0, w["enc3"], c["enc3"][0], act="softplus", scale=a["enc3"][0])
@@ -163,18 +175,24 @@ class SamplerTape:
         inp = ops.reverse_step(ops.RSTEP_INIT, yhat, M, z=noise[0], ld_out=LIN1_K)
         steps: List[Optional[tuple]] = [None] * T
         y0 = None
-        for t in range(T - 1, -1, -1):
+        for j in range(T - 1, -1, -1):
+            t = self.rows[j]
             s1 = ops.linear(inp, w["lin1"], c["lin1"][t], act="softplus", scale=a["lin1"][t])
             h2 = ops.linear(ops.cond_mul(s1, xe), w["lin2"], c["lin2"][t], act="softplus", scale=a["lin2"][t])
             h3 = ops.linear(h2, w["lin3"], c["lin3"][t], act="softplus", scale=a["lin3"][t])
             eps = ops.linear(h3, w["lin4"], self.b4)
-            if t >= 1:
+            if self.plan is not None:
+                if j >= 1:
+                    inp = ops.reverse_step_coef(yhat, inp, eps, noise[T - j], *self.coef[j], ld_out=LIN1_K)
+                else:
+                    y0 = ops.reverse_step_coef(yhat, inp, eps, None, *self.coef[0])
+            elif t >= 1:
                 inp = ops.reverse_step(ops.RSTEP_UPDATE, yhat, M, y=inp, eps=eps, z=noise[T - t], alpha_t=self.alphas[t], s_t=self.omabs[t],
                                        s_tm1=self.omabs[t - 1], ld_out=LIN1_K)
             else:
                 y0 = ops.reverse_step(ops.RSTEP_LAST, yhat, M, y=inp, eps=eps, s_t=self.omabs[0])
             if record:
-                steps[t] = (s1, h2, h3)
+                steps[j] = (s1, h2, h3)
         self._tape = dict(B=B, M=M, e0=e0, e1=e1, xe=xe, steps=steps) if record else None
         return y0
 
@@ -193,15 +211,16 @@ class SamplerTape:
         dyhat = torch.zeros(B, C, dtype=torch.float32, device=self.device)
         dxe = torch.zeros(B, self.F, dtype=torch.float32, device=self.device)
         g = dy0
-        for t in range(self.T):
-            cy, cm, ce = self.coef[t]
+        for j in range(self.S):
+            t = self.rows[j]
+            cy, cm, ce = self.coef[j][:3]
             deps, dyadd = ops.reverse_step_grad(g, C, cy, cm, ce, dyhat, ld_add=LIN1_K)
-            s1, h2, h3 = steps[t]
+            s1, h2, h3 = steps[j]
             du3 = ops.cond_act_grad(ops.linear_grad_input(deps, w["lin4"]), h3, a["lin3"][t], B)
             du2 = ops.cond_act_grad(ops.linear_grad_input(du3, w["lin3"]), h2, a["lin2"][t], B)
             du1 = ops.cond_act_grad(ops.linear_grad_input(du2, w["lin2"]), s1, a["lin1"][t], B, mul=xe, dmul_acc=dxe)
             g = ops.linear_grad_input(du1, w["lin1"], add=dyadd)               # [M, 16]: dL/dy_t, the yhat half, zeros
-            steps[t] = None
+            steps[j] = None
         ops.reverse_step_grad(g, C, 0.0, 1.0, 0.0, dyhat, want_deps=False)      # y_T = z_0 + yhat, and the last yhat half
         dn = ops.cond_act_grad(dxe, None, a["enc6"][0], B)
         du1 = ops.cond_act_grad(ops.linear_grad_input(dn, w["enc6"]), tape["e1"], a["enc3"][0], B)
@@ -234,11 +253,19 @@ class EnsembleTarget:
     reference's draw order, as Diffusion.predict_batch takes it; None draws fresh noise on EVERY call from (seed, a call counter), so an
     iterative attack averages over the defence's randomness across its steps (expectation over transformation); fix_noise() pins one
     sample path instead.  Refused, before anything is launched: the fp16 mode, ND_GEMM_F32=mfma_f32, B * mc > 128, a noise tensor of the
-    wrong shape.  The module docstring states the memory this holds."""
+    wrong shape.  The module docstring states the memory this holds.
+
+    sample_steps (default None: every timestep of the config's schedule): attack the ensemble as it is run with a sampler plan of
+    timestep_sequence(T, sample_steps, skip_type) at `eta` (diffusion_utils.sampler_plan; main --sample_steps): every chain has
+    S = self.steps steps, in time and in tape, and noise is [len(members), S, B * mc, C]."""
 
     def __init__(self, conditioner, states: Sequence[Optional[Dict[str, torch.Tensor]]], config, mc: int = 1,
-                 members: Optional[Sequence[int]] = None, temperature: Optional[float] = None, seed: int = 0):
+                 members: Optional[Sequence[int]] = None, temperature: Optional[float] = None, seed: int = 0,
+                 sample_steps: Optional[int] = None, skip_type: str = "uniform", eta: float = 1.0):
         self.members = check_target_args(conditioner, states, mc, members)
+        timesteps = None if sample_steps is None else timestep_sequence(int(config.diffusion.timesteps), sample_steps, skip_type)
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must lie in [0, 1] (eta={eta})")
         self.cond, self.mc, self.seed = conditioner, int(mc), int(seed)
         self.device = conditioner.vit.device
         if temperature is None:
@@ -255,7 +282,9 @@ class EnsembleTarget:
             if d[:4] != want or d[4] < self.T:
                 raise ValueError(f"member {k} has (C, D, H, F, T) = {d}; the config says {want} and {self.T} timesteps")
         self.C, self.D = want[0], want[1]
-        self.tapes = [SamplerTape(states[k], tables.alphas, tables.one_minus_alphas_bar_sqrt, self.device) for k in self.members]
+        self.tapes = [SamplerTape(states[k], tables.alphas, tables.one_minus_alphas_bar_sqrt, self.device, timesteps=timesteps, eta=eta)
+                      for k in self.members]
+        self.steps = self.T if timesteps is None else len(timesteps)         # reverse steps (and draws) per chain
         self._calls = 0
         self._fixed: Optional[torch.Tensor] = None
 
@@ -266,7 +295,7 @@ class EnsembleTarget:
             counter, self._calls = self._calls, self._calls + 1
         gen = torch.Generator(device=self.device)
         gen.manual_seed((self.seed * 1000003 + int(counter)) & 0x7FFFFFFFFFFFFFFF)
-        return torch.randn(len(self.members), self.T, B * self.mc, self.C, dtype=torch.float32, device=self.device, generator=gen)
+        return torch.randn(len(self.members), self.steps, B * self.mc, self.C, dtype=torch.float32, device=self.device, generator=gen)
 
     def fix_noise(self, noise: Optional[torch.Tensor] = None, B: Optional[int] = None) -> torch.Tensor:
         """Pin one sample path: every later call without a noise argument uses `noise` (or, given B, a draw from (seed, counter 0) made
@@ -284,7 +313,7 @@ class EnsembleTarget:
     def _noise(self, B: int, noise: Optional[torch.Tensor]) -> torch.Tensor:
         if noise is None:
             noise = self._fixed
-        check_call(B, self.mc, len(self.members), self.T, self.C, None if noise is None else noise.shape)
+        check_call(B, self.mc, len(self.members), self.steps, self.C, None if noise is None else noise.shape)
         return self.draw_noise(B) if noise is None else ops._f32(noise, "noise")
 
     # -- the chain ----------------------------------------------------------------------------------------------------------------------

@@ -8,7 +8,10 @@ canonical invocation testing_scripts/test.sh:24).  Implemented, with loss card_o
 aux_cls.arch == 'sevit' (the shipped configs): `--test`, `--calib`, and -- with neither -- training of the noise
 estimator `--mlp_idx` on one GPU (runner.Diffusion.train; `--snapshot_epochs N` keeps the whole training state in
 <log_path>/ckpt.pth and `--resume_training` continues from it); the other training / sampling flags are
-parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials, --snapshot_epochs.
+parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials, --snapshot_epochs, --sample_steps.
+`--sample_steps N` samples with N of the schedule's timesteps per chain (a sampler plan, diffusion_utils.sampler_plan; not a reference
+mode); only then are the reference's declared-and-never-read `--skip_type`, `--sample_type` and `--eta` read (runner.sampler_request).
+`--timesteps` is still the reference's override of diffusion.timesteps, which changes the embedding tables' shape.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N -m nested_diffusion_amd.main ...`.
 """
 from __future__ import annotations
@@ -79,6 +82,10 @@ def build_parser() -> argparse.ArgumentParser:
     # additions of this build (no reference counterpart)
     p.add_argument("--synthetic_batches", type=int, default=0, help="run on N synthetic test batches instead of a disk dataset")
     p.add_argument("--mc_trials", type=int, default=20, help="Monte-Carlo trials per member (hard-coded 20 in the reference)")
+    p.add_argument("--sample_steps", type=int, default=argparse.SUPPRESS,
+                   help="sample with N of the schedule's timesteps per chain (--test, --calib); then --skip_type uniform|quadratic, "
+                        "--sample_type generalized|ddpm_noisy (eta = 1) and --eta in [0, 1] are read.  Not given: every timestep, as always "
+                        "(and no attribute is left behind)")
     p.add_argument("--train_cache", type=str, default="none", choices=["none", "device"],
                    help="training (--mlp_idx k): 'device' decodes every image once, keeps both splits on the GPU as bytes and gathers each "
                         "batch there (same batches, same weights); 'none' decodes every epoch in a DataLoader")
@@ -169,6 +176,11 @@ def set_seed(seed: int) -> None:
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
+    from .runner import sampler_request
+    try:
+        sampler_request(args)                                     # every misuse of --sample_steps and its three flags, before the GPU is touched
+    except ValueError as e:
+        raise SystemExit(str(e))
     if args.seed is None:
         args.seed = random.randint(0, 10000)                      # main.py:163-164
     args.doc = args.doc + "/split_" + str(args.split)             # main.py:384

@@ -1,7 +1,8 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
     python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD --eps E --out ROOT \
-        [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner|ensemble] [--members 0,1,...] [--mc N]
+        [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner|ensemble] [--members 0,1,...] [--mc N] \
+        [--sample_steps N [--skip_type uniform|quadratic] [--eta E]]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
 test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
@@ -16,7 +17,9 @@ cross-entropy of the members' averaged softmax; --members selects the members (d
 --target ensemble attacks the ensemble itself, end to end (the adaptive white-box attack): the conditioner and the config's noise-estimator
 checkpoints (diffusion.trained_diffusion_ckpt_path) are wrapped in an ensemble_grad.EnsembleTarget, whose loss is -log of the probability
 test_atk reports, differentiated through the aggregation, the reverse diffusions (--mc trials per member, default 1; batch_size * mc <= 128)
-and both paths from the pixels; every gradient step draws fresh sampler noise.
+and both paths from the pixels; every gradient step draws fresh sampler noise.  --sample_steps N [--skip_type uniform|quadratic] [--eta E]
+attacks the ensemble as `main --test --sample_steps N` runs it: N of the schedule's timesteps per chain (a sampler plan,
+diffusion_utils.sampler_plan), in time and in tape.
 """
 from __future__ import annotations
 
@@ -44,7 +47,32 @@ def build_parser() -> argparse.ArgumentParser:
                         "ensemble: the whole ensemble, through the sampler")
     p.add_argument("--members", type=str, default=None, help="--target conditioner / ensemble: comma-separated member indices (default: all)")
     p.add_argument("--mc", type=int, default=argparse.SUPPRESS, help="--target ensemble: Monte-Carlo trials per member (default 1)")
+    p.add_argument("--sample_steps", type=int, default=argparse.SUPPRESS,
+                   help="--target ensemble: reverse steps per chain (a sampler plan over the schedule; default: every timestep)")
+    p.add_argument("--skip_type", type=str, default=argparse.SUPPRESS, help="with --sample_steps: uniform (default) or quadratic")
+    p.add_argument("--eta", type=float, default=argparse.SUPPRESS, help="with --sample_steps: 0 (deterministic) .. 1 (default, ancestral)")
     return p
+
+
+def sampler_args(args) -> dict:
+    """--sample_steps / --skip_type / --eta as EnsembleTarget's keywords; every misuse is refused by name (SystemExit) before the GPU is touched."""
+    from .diffusion_utils import SKIP_TYPES
+
+    if not hasattr(args, "sample_steps"):
+        for flag in ("skip_type", "eta"):
+            if hasattr(args, flag):
+                raise SystemExit(f"--{flag} is read with --sample_steps only")
+        return {}
+    if args.target != "ensemble":
+        raise SystemExit("--sample_steps sets the sampler plan of --target ensemble")
+    kw = {"sample_steps": args.sample_steps, "skip_type": getattr(args, "skip_type", "uniform"), "eta": getattr(args, "eta", 1.0)}
+    if kw["sample_steps"] < 1:
+        raise SystemExit(f"--sample_steps must be at least 1 (got {kw['sample_steps']})")
+    if kw["skip_type"] not in SKIP_TYPES:
+        raise SystemExit(f"--skip_type must be one of {SKIP_TYPES} (got {kw['skip_type']!r})")
+    if not 0.0 <= kw["eta"] <= 1.0:
+        raise SystemExit(f"--eta must lie in [0, 1] (got {kw['eta']})")
+    return kw
 
 
 def parse_members(text):
@@ -75,7 +103,7 @@ def load_target(config, device, members=None):
     return ConditionerTarget(load_conditioner(config.diffusion.trained_aux_cls_ckpt_path, checkpoint_name(config), device), members)
 
 
-def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 0):
+def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 0, **sampler):
     """--target ensemble: the conditioner and the noise estimators the runner would load for the config's dataset, as the model of a gradient
     attack on the whole ensemble (ensemble_grad.EnsembleTarget)."""
     from .ensemble_grad import EnsembleTarget
@@ -84,7 +112,7 @@ def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 
     cond = load_conditioner(config.diffusion.trained_aux_cls_ckpt_path, checkpoint_name(config), device)
     paths = config.diffusion.trained_diffusion_ckpt_path[0]
     states = [load_checkpoint_object(p)["noise_estimator"] for p in paths[:len(cond.mlps)]]
-    return EnsembleTarget(cond, states, config, mc=mc, members=members, seed=seed)
+    return EnsembleTarget(cond, states, config, mc=mc, members=members, seed=seed, **sampler)
 
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
@@ -138,12 +166,13 @@ def main(argv=None) -> int:
         raise SystemExit("--members selects members of --target conditioner or ensemble")
     if args.target != "ensemble" and hasattr(args, "mc"):
         raise SystemExit("--mc sets the trials of --target ensemble")
+    sampler = sampler_args(args)
     with open(args.config) as f:
         import yaml
         config = nd_main.dict2namespace(yaml.safe_load(f))
     device = torch.device("cuda", args.device)
     if args.target == "ensemble":
-        vit = load_ensemble_target(config, device, parse_members(args.members), getattr(args, "mc", 1), args.seed)
+        vit = load_ensemble_target(config, device, parse_members(args.members), getattr(args, "mc", 1), args.seed, **sampler)
     else:
         vit = load_vit(config, device) if args.target == "vit" else load_target(config, device, parse_members(args.members))
     if args.attack_name == "AUTOPGD":

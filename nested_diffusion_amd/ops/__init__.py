@@ -12,7 +12,7 @@ from .attack_linf import (APGD_IMPROVED, APGD_NOT_PRED, APGD_RESTORE, ApgdState,
 from .diffusion_train import (BN_EPS, BN_MOMENTUM, SUMSQ_CHUNK, bn_train_backward, bn_train_forward, clip_adam, mse_grad, qsample, sumsq,
                               sumsq_plan)
 from .ensemble_grad import (AGGREGATE_MAX_C, RSTEP_INIT, RSTEP_LAST, RSTEP_UPDATE, aggregate_xent_grad, cond_act_grad, cond_mul, reverse_step,
-                            reverse_step_grad, softmax_grad)
+                            reverse_step_coef, reverse_step_grad, softmax_grad)
 from .gemm import SplitMatrix, gemm_bias_act, gemm_split, join_rows, split_rows
 from .optim import (COLSUM_CHUNK, adam_step, adamw_step, bias_grad_adam, colsum_adamw, ensemble_xent_grad, gemm_tn_adamw, gemm_tn_plan,
                     layernorm_wgrad_adamw, linear_wgrad_adam, linear_wgrad_plan)

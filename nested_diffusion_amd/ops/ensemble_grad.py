@@ -90,6 +90,33 @@ def reverse_step(mode: int, ymean: torch.Tensor, M: int, y: Optional[torch.Tenso
     return out
 
 
+def reverse_step_coef(ymean: torch.Tensor, y: torch.Tensor, eps: torch.Tensor, z: Optional[torch.Tensor], cy: float, cm: float, ce: float,
+                      cz: float, ld_out: Optional[int] = None) -> torch.Tensor:
+    """One step of a sampler plan on the [M, C] state (nd_reverse_step_coef): fmaf(cz, z, fmaf(ce, eps, fmaf(cm, ymean[r % B], cy * y))),
+    the sampler's own device function.  Layouts as reverse_step: ymean [B, C], y [M, ld] (its first C columns), eps, z [M, C]; z None
+    needs cz == 0 (the plan's row 0, or eta = 0).  ld_out (default C): 2C <= ld_out <= 64 writes lin1's input [y, ymean[r % B], 0 ..]."""
+    ymean, y, eps, z = _f32(ymean, "ymean"), _f32(y, "y"), _f32(eps, "eps"), _opt_f32(z, "z")
+    if ymean.dim() != 2 or y.dim() != 2:
+        raise ValueError("ymean must be [B, C] and y [M, ld]")
+    B, C = ymean.shape
+    M = y.shape[0]
+    ldo = C if ld_out is None else int(ld_out)
+    if not 1 <= C <= RSTEP_MAX_C or B < 1 or M < 1 or M % B or (ldo != C and not 2 * C <= ldo <= RSTEP_MAX_LD):
+        raise ValueError(f"a reverse step takes 1 <= C <= {RSTEP_MAX_C}, M a positive multiple of B and ld_out == C or in [2C, {RSTEP_MAX_LD}] "
+                         f"(M={M}, B={B}, C={C}, ld_out={ldo})")
+    if not C <= y.shape[1] <= RSTEP_MAX_LD or y.device != ymean.device:
+        raise ValueError(f"y is {tuple(y.shape)}; expected [{M}, C <= ld <= {RSTEP_MAX_LD}] on {ymean.device}")
+    _on(eps, "eps", (M, C), ymean.device)
+    if z is None and float(cz) != 0.0:
+        raise ValueError(f"cz = {cz} needs the draw z")
+    if z is not None:
+        _on(z, "z", (M, C), ymean.device)
+    out = torch.empty(M, ldo, dtype=torch.float32, device=ymean.device)
+    check(_lib.load().nd_reverse_step_coef(ptr(y), y.shape[1], ptr(ymean), ptr(eps), ptr(z), ptr(out), ldo, M, B, C, float(cy), float(cm),
+                                           float(ce), float(cz), _stream(ymean)), "nd_reverse_step_coef")
+    return out
+
+
 def reverse_step_grad(g: torch.Tensor, C: int, cy: float, cm: float, ce: float, dymean: torch.Tensor, want_deps: bool = True,
                       ld_add: Optional[int] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """The backward of one reverse step (nd_reverse_step_bwd) from g [M, ld]: its first C columns are dL/dy_{t-1}; with ld >= 2C its

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import ops, snapshot
-from .diffusion_utils import schedule_tables
+from .diffusion_utils import SKIP_TYPES, sampler_plan, schedule_tables, timestep_sequence
 from .engine import EnsembleEngine
 from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner, require_fp32_split
 from . import dist as nd_dist
@@ -54,6 +54,31 @@ def temperature_for(dataset: str) -> float:
     raise NotImplementedError(dataset)
 
 
+SAMPLE_TYPES = ("generalized", "ddpm_noisy")
+
+
+def sampler_request(args) -> Optional[dict]:
+    """--sample_steps N [--skip_type uniform|quadratic] [--sample_type generalized|ddpm_noisy] [--eta E] as {'steps', 'skip_type', 'eta'},
+    or None when --sample_steps is not given: the other three are then not read at all, as in the reference, which declares them and
+    never reads them, and the run does what it always did.  'ddpm_noisy' means eta = 1 (ancestral sampling on the sub-chain);
+    'generalized' takes --eta (the reference's default 0.0: the deterministic chain).  Anything else is refused by name (ValueError):
+    a pure host function, called before the GPU is touched."""
+    steps = getattr(args, "sample_steps", None)
+    if steps is None:
+        return None
+    skip_type, sample_type, eta = getattr(args, "skip_type", "uniform"), getattr(args, "sample_type", "generalized"), getattr(args, "eta", 0.0)
+    if isinstance(steps, bool) or int(steps) != steps or steps < 1:
+        raise ValueError(f"--sample_steps must be an integer >= 1 (got {steps!r})")
+    if skip_type not in SKIP_TYPES:
+        raise ValueError(f"--skip_type must be one of {SKIP_TYPES} (got {skip_type!r})")
+    if sample_type not in SAMPLE_TYPES:
+        raise ValueError(f"--sample_type must be one of {SAMPLE_TYPES} (got {sample_type!r})")
+    eta = 1.0 if sample_type == "ddpm_noisy" else float(eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError(f"--eta must lie in [0, 1] (got {eta})")
+    return {"steps": int(steps), "skip_type": skip_type, "eta": eta}
+
+
 class Diffusion(object):
     def __init__(self, args, config, device=None, conditioner: Optional[GuidingConditioner] = None,
                  noise_estimator_states: Optional[List[Dict[str, torch.Tensor]]] = None):
@@ -74,6 +99,10 @@ class Diffusion(object):
         tables = schedule_tables(config.diffusion.beta_schedule, self.num_timesteps, config.diffusion.beta_start, config.diffusion.beta_end)
         self.betas, self.alphas = tables.betas.to(self.device), tables.alphas.to(self.device)
         self.one_minus_alphas_bar_sqrt = tables.one_minus_alphas_bar_sqrt.to(self.device)
+        # --sample_steps: a sampler plan over the schedule (diffusion_utils.sampler_plan; not a reference mode).  test_atk, test_calibrate,
+        # predict_batch and ensemble_target run its S steps per chain; the validation sampling inside train() stays on the full chain,
+        # whose accuracy is what picks the best checkpoint.  --timesteps is still the reference's override of diffusion.timesteps.
+        self.use_sampler(sampler_request(args))
         self.temperature = temperature_for(config.data.dataset)
         self.selected_block_indices = [0, 1, 2, 3, 4]                       # :275
         if conditioner is None:
@@ -87,6 +116,17 @@ class Diffusion(object):
         self.engine: Optional[EnsembleEngine] = None
         self.members: List[int] = []
         self.bytes_uploaded = 0          # image bytes this rank has sent over PCIe (its shard of every batch, nothing else)
+
+    def use_sampler(self, request: Optional[dict]) -> None:
+        """Sample with the plan of sampler_request's {'steps', 'skip_type', 'eta'} from here on, or (None) with every timestep again:
+        self.plan, self.sample_steps = the reverse steps per chain, and the engine's plan if the noise estimators are loaded."""
+        self.sampler, self.plan = request, None
+        if request is not None:
+            tau = timestep_sequence(self.num_timesteps, request["steps"], request["skip_type"])
+            self.plan = sampler_plan(self.one_minus_alphas_bar_sqrt, tau, request["eta"])
+        self.sample_steps = self.num_timesteps if self.plan is None else len(self.plan.timesteps)
+        if getattr(self, "engine", None) is not None:
+            self.engine.set_sampler(self.plan)
 
     # ---- conditioner -------------------------------------------------------------------------
     def compute_guiding_prediction(self, x, include_full_vit: bool = True):
@@ -126,6 +166,8 @@ class Diffusion(object):
         for slot, i in enumerate(self.members):
             self.engine.load_member(slot, self._states[i])
         self.engine.set_schedule(self.alphas, self.one_minus_alphas_bar_sqrt)
+        if self.plan is not None:
+            self.engine.set_sampler(self.plan)
         self._seeded_first = None
         self._seed_noise(0)            # in-library noise (predict_batch without a noise tensor)
         self._states = None            # device copies live in the engine
@@ -157,8 +199,10 @@ class Diffusion(object):
             states = self._read_noise_estimator_states()
         if members is None:
             members = [i for i in self.selected_block_indices if i < len(states) and i < len(self.cond_pred_model.mlps)]
+        plan = {} if self.sampler is None else {"sample_steps": self.sampler["steps"], "skip_type": self.sampler["skip_type"],
+                                                "eta": self.sampler["eta"]}
         return EnsembleTarget(self.cond_pred_model, states, self.config, mc=mc, members=members, temperature=self.temperature,
-                              seed=self.seed or 0 if seed is None else seed)
+                              seed=self.seed or 0 if seed is None else seed, **plan)
 
     def _seed_noise(self, first_image: int) -> None:
         """Seed the library's generator ONCE per (run, shard): nd_seed resets the device-side batch counter, so seeding again before
@@ -174,7 +218,7 @@ class Diffusion(object):
         GPU: per step the learning rate of lr_at (when optim.lr_schedule is set), the antithetic timestep draw, the conditioner's
         softmax as yhat, e = randn, and one train_diffusion.NoiseEstimatorTrainer.step (q_sample, the model in train mode, the
         mean-squared error, backward, clip_grad_norm_, Adam).  Every training.validation_freq epochs and on the last one the
-        validation set is sampled with the current weights (p_sample_loop in eval mode: trainer.state_dict() loaded into a one-member
+        validation set is sampled with the current weights on the FULL chain, with or without --sample_steps (p_sample_loop in eval mode: trainer.state_dict() loaded into a one-member
         EnsembleEngine, noise drawn in the library) and the top-1 accuracy of y_0 taken; a new best writes
         <log_path>/diffu{idx}_ckpt_best_eph{epoch}_acc{acc:.4f}.pth = {'noise_estimator', 'optimizer', 'epoch'}, the layout
         load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: the best file is for inference, and Adam's moments of
@@ -326,7 +370,7 @@ class Diffusion(object):
             raise RuntimeError(f"member k is conditioned on mapping MLP k: the loaded noise estimators {self.members} must be "
                                f"0..K-1 with K <= {len(self.cond_pred_model.mlps)} mapping MLPs")
         mc = mc_trials or self.mc_trials
-        eng, T = self.engine, self.num_timesteps
+        eng, T = self.engine, self.sample_steps
         images_224 = ops._f32(images_224, "images")
         cond = self.cond_pred_model.handle(images_224.shape[0], images_224.shape[-1])
         return eng.predict_batch(cond, images_224, noise, mc, T, self.temperature, use_graph=use_graph, clone=clone)
@@ -334,12 +378,12 @@ class Diffusion(object):
     # ---- world-size independent randomness ---------------------------------------------------------
     def draw_noise(self, B_total: int, lo: int, hi: int, mc: Optional[int] = None) -> torch.Tensor:
         """torch-generator draws for rows [lo, hi) of a test batch of B_total images: [K, T, (hi-lo)*mc, C], for callers that want
-        explicit noise (test_atk itself uses the library's generator, which has the same property at no cost).
+        explicit noise; T = the steps per chain, S of a sampler plan (test_atk itself uses the library's generator, which has the same property at no cost).
         Every rank holds the same --seed (the reference's set_seed, :31-38), draws the draws of the WHOLE batch
         [K, T, mc, B_total, C] and keeps its own images, so image i sees the same K*T*mc draws at any world size
         (and rows of different ranks are not copies of each other)."""
         mc = mc or self.mc_trials
-        K, T, C = len(self.members), self.num_timesteps, self.config.data.num_classes
+        K, T, C = len(self.members), self.sample_steps, self.config.data.num_classes
         z = torch.randn(K, T, mc, B_total, C, device=self.device)
         return z[:, :, :, lo:hi].reshape(K, T, mc * (hi - lo), C).contiguous()
 
@@ -413,7 +457,7 @@ class Diffusion(object):
         if direct:
             eng = self.engine
             eng.enable_input_flag()
-            fixed = eng.batch_buffers(hi - lo, self.mc_trials, self.num_timesteps, tuple(x0.shape[1:]))["images"]
+            fixed = eng.batch_buffers(hi - lo, self.mc_trials, self.sample_steps, tuple(x0.shape[1:]))["images"]
             k, item = 0, first
             while item is not None:
                 x, t = rows_of(item)
@@ -565,7 +609,7 @@ class Diffusion(object):
             C = out["prob"].shape[1]
             prob_mc.append(packed[:, :C]); piw_mc.append(packed[:, C:2 * C]); var_mc.append(packed[:, 2 * C:3 * C])
             mv_class.append(packed[:, 3 * C].to(torch.int64)); target_class.append(packed[:, 3 * C + 1].to(torch.int64))
-            n_step_img += B * len(self.members) * self.mc_trials * self.num_timesteps
+            n_step_img += B * len(self.members) * self.mc_trials * self.sample_steps      # the steps that ran: S of a plan, else T
         torch.cuda.synchronize(self.device)
         dt = time.time() - t0
         if self.engine.loop_form() == "one_launch":
