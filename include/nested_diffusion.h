@@ -757,7 +757,7 @@ size_t nd_layernorm_wgrad_workspace_bytes(int rows, int dim);
  * diffusion/classification_train_separately.py:967-1006 for latent_model.py's ConditionalModel, arch 'linear').  The Linear layers run on
  * nd_linear, nd_linear_bwd and the gradient-only mode of nd_linear_wgrad_adam / nd_bias_grad_adam above; these entry points are what the
  * model has beyond them.  fp32 row-major data.  None of them allocates, copies synchronously or synchronises; no atomics; every loop is
- * bounded by the shape arguments; the same bits on every run.  Each line of nd_qsample, nd_mse_grad, nd_sumsq and nd_clip_adam is one
+ * bounded by the shape arguments; the same bits on every run.  Each line of nd_qsample, nd_mse_grad, nd_sumsq, nd_clip_adam and nd_clip_adam_ema is one
  * rounded fp32 operation, no contraction, division and square root correctly rounded; the optimizer listing is nd_linear_wgrad_adam's
  * (csrc/nd_optim.hpp), not a second copy.  The two BatchNorm entry points read and write fp32 and carry a column's statistics and sums
  * in DOUBLE, rounding once where a value is stored (torch's CPU BatchNorm accumulates float data in double too): with few rows that
@@ -808,7 +808,8 @@ size_t nd_layernorm_wgrad_workspace_bytes(int rows, int dim);
  *                         c = max_norm / (total + 1e-6)
  *                         coef = (c < 1) ? c : 1                         (a NaN gives 1, as torch 1.10's `if clip_coef < 1`)
  *                         g' = g * coef
- *                     then nd_linear_wgrad_adam's listing on (w, m, v, g').  sumsq == NULL: no clipping (g' = g). */
+ *                     then nd_linear_wgrad_adam's listing on (w, m, v, g').  sumsq == NULL: no clipping (g' = g).
+ *   nd_clip_adam_ema  the same pass with the EMA shadow of w updated from the new weight (declared and described below nd_clip_adam). */
 #define ND_SUMSQ_CHUNK 4096
 #define ND_SUMSQ_MAX_N ((size_t)1 << 40)
 #define ND_MSE_MAX_C 1024
@@ -827,6 +828,23 @@ int nd_sumsq_plan(size_t n, size_t *out2);
 size_t nd_sumsq_workspace_bytes(size_t n);
 int nd_clip_adam(float *w_dev, float *m_dev, float *v_dev, const float *g_dev, size_t n, const float *sumsq_dev, float max_norm,
                  const nd_adam_step *a, void *stream);
+/* nd_clip_adam with the exponential moving average of the parameters riding in the same pass (diffusion/ema.py EMA.update after
+ * optimizer.step(), classification_train_separately.py:1006-1011): nd_clip_adam's listing on (w, m, v, g), unchanged, then on the NEW weight
+ *     pw = one_minus_mu * w
+ *     ps = mu * s
+ *     s = pw + ps
+ * three rounded fp32 operations, no contraction, denormals kept (torch's two scalar products and their sum).  nd_ema_step is formed by the
+ * host in double and each field rounded once: one_minus_mu = (float)(1.0 - mu), which is NOT 1.0f - (float)mu ((float)(1.0 - 0.9999) is
+ * 1e-04f, 1.0f - 0.9999f is 1.00016594e-04f).  The shadow s is a fifth buffer of n floats in w's layout: the pass moves nine four-byte
+ * streams per element where nd_clip_adam moves seven, and w is not read a second time.  The zero padding of an image stays 0 in s
+ * (c1 * 0 + c2 * 0).  float4 accesses when n % 4 == 0 and all five buffers are 16-byte aligned, scalar ones otherwise.  ND_ERR_ARG before
+ * any launch: a NULL s or e (or any NULL nd_clip_adam refuses), n < 1, a pointer that is not 4-byte aligned, any two of w, m, v, g, s
+ * equal.  No allocation, no synchronisation: capturable like nd_clip_adam. */
+typedef struct nd_ema_step {
+    float one_minus_mu, mu;
+} nd_ema_step;
+int nd_clip_adam_ema(float *w_dev, float *m_dev, float *v_dev, const float *g_dev, float *s_dev, size_t n, const float *sumsq_dev,
+                     float max_norm, const nd_adam_step *a, const nd_ema_step *e, void *stream);
 
 /* ---- the input gradient of the ensemble, through the sampler (csrc/nd_ensemble_grad.hip; the chain: ensemble_grad.py SamplerTape and
  * EnsembleTarget).  The reference has the hook and never uses it: p_sample(..., output_detach=False), diffusion/diffusion_utils.py:80-83,

@@ -93,6 +93,11 @@ class NdAdamwStep(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "step_size", "sqrt_bc2", "eps", "decay")]
 
 
+class NdEmaStep(C.Structure):
+    """nd_ema_step: the two coefficients of the EMA shadow's update, each rounded once from double (ops.ema_step)"""
+    _fields_ = [(n, C.c_float) for n in ("one_minus_mu", "mu")]
+
+
 class NdBatchOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("samples", "prob", "vote", "probs", "yhat")]
 
@@ -215,6 +220,7 @@ SIGNATURES = {
     "nd_sumsq_plan": (_i, [_sz, C.POINTER(_sz)]),
     "nd_sumsq_workspace_bytes": (_sz, [_sz]),
     "nd_clip_adam": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _f, C.POINTER(NdAdamStep), _vp]),
+    "nd_clip_adam_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _f, C.POINTER(NdAdamStep), C.POINTER(NdEmaStep), _vp]),
     "nd_cond_mul": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "nd_cond_act_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nd_reverse_step": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp]),

@@ -1,5 +1,5 @@
 // nd_diffusion_train.hip -- training of the noise estimators (include/nested_diffusion.h: nd_bn_train_fwd, nd_bn_train_bwd, nd_qsample,
-// nd_mse_grad, nd_sumsq, nd_clip_adam; the loop: nested_diffusion_amd/train_diffusion.py NoiseEstimatorTrainer).  gfx950 only, fp32 data.
+// nd_mse_grad, nd_sumsq, nd_clip_adam, nd_clip_adam_ema; the loop: nested_diffusion_amd/train_diffusion.py NoiseEstimatorTrainer).  gfx950 only, fp32 data.
 //   k_bn_fwd / k_bn_bwd   BatchNorm1d in training mode fused with ConditionalLinear's per-timestep gain, the softplus and the product with
 //                         xe.  A batch has at most 128 rows, so ONE THREAD owns a column and walks its rows in order: the loads of a wave
 //                         are 64 adjacent floats of a row (coalesced), no cross-thread reduction exists, and the dense gradient of the
@@ -10,7 +10,8 @@
 //                         times those of torch's CPU BatchNorm, which accumulates float data in double as well.
 //   k_qsample / k_mse     the forward noising with host-gathered per-row coefficients, and the loss with its gradient
 //   k_sumsq_*             sum of squares in two stages through a caller workspace, in an order that depends on n alone
-//   k_clip_adam           clip coefficient from the summed squares, then nd_optim.hpp's Adam listing, elementwise
+//   k_clip_adam           clip coefficient from the summed squares, then nd_optim.hpp's Adam listing, elementwise; its EMA instantiations
+//                         end with nd_optim.hpp's shadow update on the new weight, in the same pass
 // Bounds: every index below is r * N + n with r < M, n < N, or tr * N + n with 0 <= tr < rows_table checked in the kernel (a row whose
 // timestep is outside the table reads and writes no table row), or i < n.
 #include "nd_math.hpp"
@@ -199,9 +200,11 @@ __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
     return (c < 1.0f) ? c : 1.0f;
 }
 
-template <bool VEC>
+// EMA: the shadow s rides in the same pass (nd_clip_adam_ema): one more load and one more store per element, no second read of w
+template <bool VEC, bool EMA>
 __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g,
-                                                   size_t n, const float* __restrict__ sumsq, float max_norm, int clip, nd_adam_step a) {
+                                                   float* __restrict__ s, size_t n, const float* __restrict__ sumsq, float max_norm, int clip,
+                                                   nd_adam_step a, nd_ema_step e) {
     const float coef = clip_coef(clip ? sumsq : nullptr, max_norm);
     const size_t stride = (size_t)gridDim.x * 256;
     if (VEC) {                                      // n % 4 == 0 and 16-byte aligned tensors
@@ -209,6 +212,8 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ w, float*
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
             float4 w4 = reinterpret_cast<float4*>(w)[i], m4 = reinterpret_cast<float4*>(m)[i], v4 = reinterpret_cast<float4*>(v)[i];
             const float4 g4 = reinterpret_cast<const float4*>(g)[i];
+            float4 s4;
+            if (EMA) s4 = reinterpret_cast<float4*>(s)[i];
             const float gx = clip ? g4.x * coef : g4.x, gy = clip ? g4.y * coef : g4.y, gz = clip ? g4.z * coef : g4.z,
                         gw = clip ? g4.w * coef : g4.w;
             nd_optim_update(w4.x, m4.x, v4.x, gx, a);
@@ -218,6 +223,13 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ w, float*
             reinterpret_cast<float4*>(w)[i] = w4;
             reinterpret_cast<float4*>(m)[i] = m4;
             reinterpret_cast<float4*>(v)[i] = v4;
+            if (EMA) {
+                nd_ema_update(s4.x, w4.x, e);
+                nd_ema_update(s4.y, w4.y, e);
+                nd_ema_update(s4.z, w4.z, e);
+                nd_ema_update(s4.w, w4.w, e);
+                reinterpret_cast<float4*>(s)[i] = s4;
+            }
         }
     } else {
         for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
@@ -227,6 +239,11 @@ __global__ __launch_bounds__(256) void k_clip_adam(float* __restrict__ w, float*
             w[i] = wv;
             m[i] = mv;
             v[i] = vv;
+            if (EMA) {
+                float sv = s[i];
+                nd_ema_update(sv, wv, e);
+                s[i] = sv;
+            }
         }
     }
 }
@@ -343,19 +360,41 @@ extern "C" int nd_sumsq(const float* x, size_t n, float* acc, int accumulate, vo
     return ND_OK;
 }
 
-extern "C" int nd_clip_adam(float* w, float* m, float* v, const float* g, size_t n, const float* sumsq, float max_norm, const nd_adam_step* a,
-                            void* stream) {
-    if (!w || !m || !v || !g || !a) return nd_set_err(ND_ERR_ARG, "clip_adam: NULL tensor");
-    if (n < 1) return nd_set_err(ND_ERR_ARG, "clip_adam needs n >= 1");
-    if (nd_misaligned(w, 3) || nd_misaligned(m, 3) || nd_misaligned(v, 3) || nd_misaligned(g, 3) || nd_misaligned(sumsq, 3))
-        return nd_set_err(ND_ERR_ARG, "clip_adam: misaligned tensor");
-    const void* p[4] = {w, m, v, g};
-    if (nd_any_equal(p, 4)) return nd_set_err(ND_ERR_ARG, "clip_adam: w, m, v and g must be distinct buffers");
-    const bool vec = n % 4 == 0 && !nd_misaligned(w, 15) && !nd_misaligned(m, 15) && !nd_misaligned(v, 15) && !nd_misaligned(g, 15);
+// the checks and the launch nd_clip_adam and nd_clip_adam_ema share; s and e NULL: no shadow (what: the entry point's name in a refusal)
+static int clip_adam_launch(const char* what, float* w, float* m, float* v, const float* g, float* s, size_t n, const float* sumsq, float max_norm,
+                            const nd_adam_step* a, const nd_ema_step* e, void* stream) {
+    const bool ema = e != nullptr;
+    if (!w || !m || !v || !g || !a || (ema && !s)) return nd_set_err(ND_ERR_ARG, "%s: NULL tensor", what);
+    if (n < 1) return nd_set_err(ND_ERR_ARG, "%s needs n >= 1", what);
+    if (nd_misaligned(w, 3) || nd_misaligned(m, 3) || nd_misaligned(v, 3) || nd_misaligned(g, 3) || nd_misaligned(sumsq, 3) ||
+        (ema && nd_misaligned(s, 3)))
+        return nd_set_err(ND_ERR_ARG, "%s: misaligned tensor", what);
+    const void* p[5] = {w, m, v, g, s};
+    if (nd_any_equal(p, ema ? 5 : 4)) return nd_set_err(ND_ERR_ARG, "%s: w, m, v%s and g must be distinct buffers", what, ema ? ", s" : "");
+    const bool vec = n % 4 == 0 && !nd_misaligned(w, 15) && !nd_misaligned(m, 15) && !nd_misaligned(v, 15) && !nd_misaligned(g, 15) &&
+                     !(ema && nd_misaligned(s, 15));
     const unsigned blocks = nd_blocks_per_image(vec ? n / 4 : n, 16384);
     hipStream_t st = (hipStream_t)stream;
-    if (vec) hipLaunchKernelGGL((k_clip_adam<true>), dim3(blocks), dim3(256), 0, st, w, m, v, g, n, sumsq, max_norm, sumsq ? 1 : 0, *a);
-    else hipLaunchKernelGGL((k_clip_adam<false>), dim3(blocks), dim3(256), 0, st, w, m, v, g, n, sumsq, max_norm, sumsq ? 1 : 0, *a);
+    const int clip = sumsq ? 1 : 0;
+    const nd_ema_step ev = ema ? *e : nd_ema_step{};
+    if (ema) {
+        if (vec) hipLaunchKernelGGL((k_clip_adam<true, true>), dim3(blocks), dim3(256), 0, st, w, m, v, g, s, n, sumsq, max_norm, clip, *a, ev);
+        else hipLaunchKernelGGL((k_clip_adam<false, true>), dim3(blocks), dim3(256), 0, st, w, m, v, g, s, n, sumsq, max_norm, clip, *a, ev);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_clip_adam<true, false>), dim3(blocks), dim3(256), 0, st, w, m, v, g, s, n, sumsq, max_norm, clip, *a, ev);
+        else hipLaunchKernelGGL((k_clip_adam<false, false>), dim3(blocks), dim3(256), 0, st, w, m, v, g, s, n, sumsq, max_norm, clip, *a, ev);
+    }
     HIP_CHECK(hipGetLastError());
     return ND_OK;
+}
+
+extern "C" int nd_clip_adam(float* w, float* m, float* v, const float* g, size_t n, const float* sumsq, float max_norm, const nd_adam_step* a,
+                            void* stream) {
+    return clip_adam_launch("clip_adam", w, m, v, g, nullptr, n, sumsq, max_norm, a, nullptr, stream);
+}
+
+extern "C" int nd_clip_adam_ema(float* w, float* m, float* v, const float* g, float* s, size_t n, const float* sumsq, float max_norm,
+                                const nd_adam_step* a, const nd_ema_step* e, void* stream) {
+    if (!s || !e) return nd_set_err(ND_ERR_ARG, "clip_adam_ema: NULL %s", !s ? "shadow s" : "nd_ema_step");
+    return clip_adam_launch("clip_adam_ema", w, m, v, g, s, n, sumsq, max_norm, a, e, stream);
 }

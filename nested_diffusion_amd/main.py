@@ -8,7 +8,8 @@ canonical invocation testing_scripts/test.sh:24).  Implemented, with loss card_o
 aux_cls.arch == 'sevit' (the shipped configs): `--test`, `--calib`, and -- with neither -- training of the noise
 estimator `--mlp_idx` on one GPU (runner.Diffusion.train; `--snapshot_epochs N` keeps the whole training state in
 <log_path>/ckpt.pth and `--resume_training` continues from it); the other training / sampling flags are
-parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials, --snapshot_epochs, --sample_steps.
+parsed for compatibility and rejected at dispatch.  Additions: --synthetic_batches, --mc_trials, --snapshot_epochs, --sample_steps, --ema, --use_ema.
+`--ema` (training) keeps the reference's EMA shadow of the parameters at model.ema_rate; `--use_ema` (--test, --calib) samples from it.
 `--sample_steps N` samples with N of the schedule's timesteps per chain (a sampler plan, diffusion_utils.sampler_plan; not a reference
 mode); only then are the reference's declared-and-never-read `--skip_type`, `--sample_type` and `--eta` read (runner.sampler_request).
 `--timesteps` is still the reference's override of diffusion.timesteps, which changes the embedding tables' shape.
@@ -94,6 +95,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="training (--mlp_idx k): write the whole training state (weights, Adam's moments, counters, generators) to "
                         "<log_path>/ckpt.pth every N epochs and after the last one; --resume_training continues from that file "
                         "(default 0: never; a flag that is not given leaves no attribute behind)")
+    p.add_argument("--ema", action="store_true", default=argparse.SUPPRESS,
+                   help="training (--mlp_idx k): keep the reference's EMA shadow of the parameters at the config's model.ema_rate, updated in "
+                        "the optimizer's pass; the best checkpoint gains an 'ema' entry and ckpt.pth carries the shadow.  Not given: no shadow, "
+                        "whatever model.ema says in the config (and no attribute is left behind)")
+    p.add_argument("--use_ema", action="store_true", default=argparse.SUPPRESS,
+                   help="--test / --calib: read the 'ema' entry of the noise-estimator checkpoints (written by --ema) instead of "
+                        "'noise_estimator' (not given: the live weights, and no attribute is left behind)")
     return p
 
 

@@ -14,8 +14,8 @@ from .diffusion_train import (BN_EPS, BN_MOMENTUM, SUMSQ_CHUNK, bn_train_backwar
 from .ensemble_grad import (AGGREGATE_MAX_C, RSTEP_INIT, RSTEP_LAST, RSTEP_UPDATE, aggregate_xent_grad, cond_act_grad, cond_mul, reverse_step,
                             reverse_step_coef, reverse_step_grad, softmax_grad)
 from .gemm import SplitMatrix, gemm_bias_act, gemm_split, join_rows, split_rows
-from .optim import (COLSUM_CHUNK, adam_step, adamw_step, bias_grad_adam, colsum_adamw, ensemble_xent_grad, gemm_tn_adamw, gemm_tn_plan,
-                    layernorm_wgrad_adamw, linear_wgrad_adam, linear_wgrad_plan)
+from .optim import (COLSUM_CHUNK, adam_step, adamw_step, bias_grad_adam, colsum_adamw, ema_step, ensemble_xent_grad, gemm_tn_adamw,
+                    gemm_tn_plan, layernorm_wgrad_adamw, linear_wgrad_adam, linear_wgrad_plan)
 from .packed_linear import LINEAR_BWD_MAX_M, PackedWeight, linear, linear_grad_input
 from .report_tail import aggregate, report, sample_stats, softmax_rows
 from .square import SQUARE_ACCEPT, SQUARE_ACTIVE, SquareState, square_accept, square_commit, square_init, square_propose

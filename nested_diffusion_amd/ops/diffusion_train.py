@@ -159,30 +159,47 @@ def sumsq(x, acc: Optional[torch.Tensor] = None, accumulate: bool = False) -> to
     return acc
 
 
-def clip_adam(w, m, v, g, adam, sumsq: Optional[torch.Tensor] = None, max_norm: float = 1.0) -> None:
+def clip_adam(w, m, v, g, adam, sumsq: Optional[torch.Tensor] = None, max_norm: float = 1.0, shadow=None, ema=None) -> None:
     """clip_grad_norm_'s scaling by min(1, max_norm / (sqrt(sumsq) + 1e-6)) and one Adam step on a materialised gradient, in place on w,
     m, v (nd_clip_adam).  w, m, v, g: four float32 GPU tensors of one shape, or four PackedWeight images of one shape (elementwise: the
-    layout does not matter).  sumsq: the device scalar ops.sumsq accumulated over ALL gradients, or None for no clipping."""
+    layout does not matter).  sumsq: the device scalar ops.sumsq accumulated over ALL gradients, or None for no clipping.
+    shadow with ema = ops.ema_step(mu): the same pass also moves the EMA shadow of w towards the new weight, in place
+    (nd_clip_adam_ema: shadow = (1 - mu) * w_new + mu * shadow); shadow obeys m's and v's rules and is a fifth distinct buffer (a packed
+    image's zero padding stays zero).  Both come together; neither: nd_clip_adam as it always was."""
     if not isinstance(adam, _lib.NdAdamStep):
         raise TypeError("adam must be an ops.adam_step(...)")
+    if (shadow is None) != (ema is None):
+        raise ValueError("clip_adam: shadow and ema come together (ema = ops.ema_step(mu))")
+    if ema is not None and not isinstance(ema, _lib.NdEmaStep):
+        raise TypeError("ema must be an ops.ema_step(...)")
+    state = ((m, "m"), (v, "v")) + (((shadow, "shadow"),) if ema is not None else ())
     if isinstance(w, PackedWeight):
-        for p, name in ((m, "m"), (v, "v"), (g, "g")):
+        for p, name in state + ((g, "g"),):
             if not isinstance(p, PackedWeight) or (p.N, p.K, p.dtype) != (w.N, w.K, w.dtype):
                 raise ValueError(f"{name} must be a PackedWeight image of w's shape [{w.N}, {w.K}]")
         if w.dtype != _lib.ND_DTYPE_F32:
             raise _lib.NdError("clip_adam updates fp32 weight images only")
-        w, m, v, g = w.data, m.data, v.data, g.data
+        w, g = w.data, g.data
+        state = tuple((p.data, name) for p, name in state)
+    elif isinstance(shadow, PackedWeight):
+        raise ValueError("shadow is a PackedWeight image, w a tensor: the five buffers are tensors or images alike")
     g = _f32(g, "g")
-    for p, name in ((w, "w"), (m, "m"), (v, "v")):
+    state = ((w, "w"),) + state
+    for p, name in state:
         _inplace(p, name, shape=tuple(g.shape))
         if p.device != g.device:
             raise ValueError(f"{name} is on {p.device}, g on {g.device}")
-    if len({w.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr()}) != 4:
-        raise ValueError("clip_adam: w, m, v and g must be distinct buffers")
+    if len({p.data_ptr() for p, _ in state} | {g.data_ptr()}) != len(state) + 1:
+        raise ValueError("clip_adam: w, m, v" + (", shadow" if ema is not None else "") + " and g must be distinct buffers")
     if g.numel() < 1:
         raise ValueError("clip_adam of an empty tensor")
     sumsq = _opt_f32(sumsq, "sumsq")
     if sumsq is not None and (sumsq.numel() != 1 or sumsq.device != g.device):
         raise ValueError(f"sumsq must be one float32 on {g.device}")
-    check(_lib.load().nd_clip_adam(ptr(w), ptr(m), ptr(v), ptr(g), g.numel(), ptr(sumsq), float(max_norm), ctypes.byref(adam), _stream(g)),
-          "nd_clip_adam")
+    lib, (w, m, v) = _lib.load(), [p for p, _ in state[:3]]
+    if ema is None:
+        check(lib.nd_clip_adam(ptr(w), ptr(m), ptr(v), ptr(g), g.numel(), ptr(sumsq), float(max_norm), ctypes.byref(adam), _stream(g)),
+              "nd_clip_adam")
+    else:
+        check(lib.nd_clip_adam_ema(ptr(w), ptr(m), ptr(v), ptr(g), ptr(state[3][0]), g.numel(), ptr(sumsq), float(max_norm),
+                                   ctypes.byref(adam), ctypes.byref(ema), _stream(g)), "nd_clip_adam_ema")

@@ -4,6 +4,7 @@ through the mapping MLPs", "training of the mapping MLPs", "training of the ViT"
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -60,6 +61,15 @@ def adamw_step(lr: float, t: int, weight_decay: float = 0.1, betas: Tuple[float,
     if weight_decay < 0.0:
         raise ValueError(f"adamw_step needs weight_decay >= 0 (weight_decay={weight_decay})")
     return _lib.NdAdamwStep(*_adam_fields("adamw_step", lr, t, betas, eps), 1.0 - float(lr) * float(weight_decay))
+
+
+def ema_step(mu: float) -> "_lib.NdEmaStep":
+    """nd_ema_step of the rate mu in (0, 1) (diffusion/ema.py EMA(mu)): 1 - mu is formed in double, as Python forms `1. - self.mu`, and
+    each coefficient is rounded to fp32 once -- (float)(1.0 - mu), not 1.0f - (float)mu."""
+    mu = float(mu)
+    if not (math.isfinite(mu) and 0.0 < mu < 1.0):
+        raise ValueError(f"ema_step needs a finite rate with 0 < mu < 1 (mu={mu})")
+    return _lib.NdEmaStep(1.0 - mu, mu)
 
 
 _STEP_ARG = {_lib.NdAdamStep: "adam", _lib.NdAdamwStep: "adamw"}

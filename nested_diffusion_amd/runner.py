@@ -173,12 +173,18 @@ class Diffusion(object):
         self._states = None            # device copies live in the engine
 
     def _read_noise_estimator_states(self) -> List[Dict[str, torch.Tensor]]:
-        """:684-697: the 'noise_estimator' state_dicts of the config's checkpoints, in member order."""
+        """:684-697: the 'noise_estimator' state_dicts of the config's checkpoints, in member order; with args.use_ema their 'ema'
+        entries instead (the averaged weights a training run with --ema saved beside the live ones; a KeyError names the file that
+        has none).  Every reader of the checkpoints goes through here: --test, --calib and ensemble_target."""
         paths = self.config.diffusion.trained_diffusion_ckpt_path[0]
+        entry = "ema" if getattr(self.args, "use_ema", False) else "noise_estimator"
         states = []
         for i in range(min(len(paths), self.num_noise_estimators_required)):
             state = load_checkpoint_object(paths[i])      # {'noise_estimator': state_dict, 'optimizer': ..., 'epoch': ...} (:1120-1126)
-            states.append(state["noise_estimator"])
+            if entry not in state:
+                raise KeyError(f"{paths[i]} holds no '{entry}' entry" + (": --use_ema needs a checkpoint written by a training run with --ema"
+                                                                          if entry == "ema" else ""))
+            states.append(state[entry])
             logging.info("Diffusion model %d loaded", i)
         return states
 
@@ -226,8 +232,12 @@ class Diffusion(object):
         name, :890-908), every args.snapshot_epochs epochs and after the last: {'trainer': trainer.training_state(), 'loop':
         {'next_epoch', 'step', 'max_accuracy', 'best', 'losses', 'accuracies'}, 'rng': snapshot.rng_state, the validation engine's
         sampler state included}; args.resume_training continues from it at the top of epoch 'next_epoch' (a FileNotFoundError
-        names the file if there is none), with lr_at on the true epoch index, and returns the earlier epochs too.  No EMA shadow
-        is kept: the reference updates one and never reads it.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
+        names the file if there is none), with lr_at on the true epoch index, and returns the earlier epochs too.  args.ema
+        (main --ema) keeps the reference's EMA shadow of the parameters at config.model.ema_rate (a missing rate or one outside (0, 1) is
+        refused by name before anything is built): every step's optimizer pass updates it, the best file gains a fourth entry 'ema' =
+        trainer.ema_state_dict() (what --use_ema reads), ckpt.pth carries it and a resumed run restores it.  Validation and the choice of
+        the best epoch stay on the live weights, as in the reference: the losses, accuracies, best epochs and 'noise_estimator' bits
+        are those of a run without the flag.  Without it nothing is kept, whatever model.ema says in the config.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
         (default: <dataroot>/training shuffled in batches of training.batch_size, <dataroot>/validation in batches of
         testing.batch_size, drop_last; with --train_cache device the same batches in the same order from data.DeviceImageSet, decoded once
         and gathered on the GPU, --cache_dir keeping the decoded sets for later runs).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
@@ -249,6 +259,11 @@ class Diffusion(object):
         snap_path = os.path.join(args.log_path, "ckpt.pth")                   # the reference's file name (:890-908, commented out there)
         snapshot_epochs = int(getattr(args, "snapshot_epochs", 0) or 0)
         snap = snapshot.read(snap_path) if getattr(args, "resume_training", False) else None
+        ema_rate = None
+        if getattr(args, "ema", False):
+            ema_rate = getattr(config.model, "ema_rate", None)
+            if isinstance(ema_rate, bool) or not isinstance(ema_rate, (int, float)) or not 0.0 < float(ema_rate) < 1.0:
+                raise ValueError(f"model.ema_rate: --ema needs a rate in (0, 1) in the config (model.ema_rate={ema_rate!r})")
         print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
         B_valid = config.testing.batch_size
         if train_loader is None or valid_loader is None:
@@ -271,7 +286,7 @@ class Diffusion(object):
                 train_loader = loader("training", config.training.batch_size, shuffle=True)
             if valid_loader is None:
                 valid_loader = loader("validation", B_valid, shuffle=False, drop_last=True)
-        trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0)
+        trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0, ema_rate=ema_rate)
         self.trainer = trainer                     # stays reachable after the run: its training_state() is what a snapshot holds
         batch_size = snapshot.loader_batch_size(train_loader)
         trainer.run_meta = {"mlp_idx": int(mlp_idx), "dataset": config.data.dataset, "train_batches": len(train_loader),
@@ -342,6 +357,8 @@ class Diffusion(object):
                 if acc_avg > max_accuracy:
                     logging.info("Update accuracy at Epoch {}.".format(epoch))
                     states = {'noise_estimator': trainer.state_dict(), 'optimizer': {'step': trainer.t, 'lr': trainer.lr}, 'epoch': epoch}
+                    if ema_rate is not None:
+                        states['ema'] = trainer.ema_state_dict()
                     best = os.path.join(args.log_path, "diffu{}_ckpt_best_eph{}_acc{:.4f}.pth".format(mlp_idx, epoch, acc_avg))
                     torch.save(states, best)
                     print("Saved diffusion model {} at {}".format(mlp_idx, best))

@@ -16,12 +16,14 @@ import torch
 FORMAT = 1
 KINDS = ("noise_estimator", "mapping", "vit")
 EXTENDABLE = ("epochs",)          # recorded for the reader, never compared: a resumed run may ask for more epochs than the first one did
+OPTIONAL = ("ema_rate",)          # recorded only by a run that has it (an EMA shadow): a snapshot with one belongs to no run without
 
 
 def check_meta(saved: dict, expected: dict) -> None:
     """Does a snapshot's 'meta' belong to this run?  Raises a ValueError that names the first field that differs: the format, the kind
     of trainer, a dimension, the member index (mlp_idx / mn_idx), the dataset, the batch size or the training loader's length
-    (train_batches).  The epoch count is not compared: a run can be extended."""
+    (train_batches), the EMA rate (ema_rate: recorded by a run that keeps a shadow, and then refused by one that keeps none as well as
+    the reverse).  The epoch count is not compared: a run can be extended."""
     if not isinstance(saved, dict):
         raise ValueError("meta: the snapshot holds no 'meta' entry")
     if saved.get("format") != FORMAT:
@@ -33,6 +35,9 @@ def check_meta(saved: dict, expected: dict) -> None:
             raise ValueError(f"{field}: the snapshot does not record it (this run has {field}={want!r})")
         if saved[field] != want:
             raise ValueError(f"{field}: the snapshot was taken with {field}={saved[field]!r}, this run has {field}={want!r}")
+    for field in OPTIONAL:
+        if field in saved and field not in expected:
+            raise ValueError(f"{field}: the snapshot was taken with {field}={saved[field]!r}, this run has none")
 
 
 def atomic_save(obj, path: str) -> None:

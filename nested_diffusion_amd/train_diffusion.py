@@ -14,10 +14,14 @@ scales and applies them.  All of it is fp32 arithmetic in documented orders, exc
 and sums in double (include/nested_diffusion.h says why).  Nothing is read back inside a step; no torch gather or index op runs on the device: the timesteps stay on the
 CPU until check_step_args has passed them, and the schedule coefficients of a batch are gathered there.
 
-Left out: the EMA shadow.  The reference updates one on every step (:1007-1011) but never reads it -- the checkpoint saves
-noise_estimator.state_dict() (:1120) -- so it has no effect on anything the reference writes.  Also out of scope:
-train_guidance_only, more than one GPU, the fp16 mode.  training_state() / load_training_state() carry a run across an interruption
-(snapshot.py; Diffusion.train writes and reads the file)."""
+The EMA shadow (diffusion/ema.py; registered at :879-883, updated after every optimizer step at :1006-1011) is kept on request:
+NoiseEstimatorTrainer(..., ema_rate=mu) clones every parameter at construction, each ops.clip_adam call of a step then carries the
+parameter's shadow through the same pass (nd_clip_adam_ema: no second read of the weights), ema_state_dict() is what the reference's
+EMA.ema(model); model.state_dict() gives, and training_state() / load_training_state() carry the shadow as 'ema'.  It costs one more
+copy of the parameters on the device.  Without a rate nothing of it exists: the same launches, allocations and state keys as ever.
+The reference never reads its shadow back in training -- the checkpoint saves noise_estimator.state_dict() (:1120) -- so the shadow
+changes nothing else a run writes.  Out of scope: train_guidance_only, more than one GPU, the fp16 mode.  training_state() /
+load_training_state() carry a run across an interruption (snapshot.py; Diffusion.train writes and reads the file)."""
 from __future__ import annotations
 
 import math
@@ -113,10 +117,15 @@ class NoiseEstimatorTrainer:
     """One ConditionalModel(config, guidance=True) in training mode with Adam's state beside it.  The seven Linear weights live as packed
     images (ops.PackedWeight); lin1.lin.weight [F, 2C] is held padded to LIN1_K columns and its input cat(y_t, yhat) zero-padded to match:
     the padded columns' gradient is exactly +0 and Adam leaves them at 0; state_dict() cuts them off.  `lr` is the learning rate of the
-    next step (the loop sets it from lr_at); every other hyper-parameter comes from config.optim."""
+    next step (the loop sets it from lr_at); every other hyper-parameter comes from config.optim.  ema_rate: keep the EMA shadow of every
+    parameter at that rate in self.shadow (None: no shadow, and nothing of it in any launch, allocation or saved state)."""
 
-    def __init__(self, config, device, seed: int = 0, state_dict: Optional[Dict[str, torch.Tensor]] = None):
+    def __init__(self, config, device, seed: int = 0, state_dict: Optional[Dict[str, torch.Tensor]] = None,
+                 ema_rate: Optional[float] = None):
         _refuse_config(config)
+        self.ema_rate = None if ema_rate is None else float(ema_rate)
+        if self.ema_rate is not None:
+            ops.ema_step(self.ema_rate)                                             # refuses a rate outside (0, 1) before anything is built
         self.device = torch.device(device)
         self.C, self.D = int(config.data.num_classes), int(config.model.data_dim)
         self.H, self.F, self.T = int(config.model.hidden_dim), int(config.model.feature_dim), int(config.diffusion.timesteps)
@@ -166,7 +175,20 @@ class NoiseEstimatorTrainer:
         zeros = lambda q: q.zeros_like() if isinstance(q, ops.PackedWeight) else torch.zeros_like(q)    # noqa: E731
         self.m = {k: zeros(q) for k, q in self.p.items()}
         self.v = {k: zeros(q) for k, q in self.p.items()}
+        # EMA.register right after the model is built (:880-881): a clone of every parameter, packed images staying packed
+        self.shadow: Optional[Dict[str, object]] = None
+        if self.ema_rate is not None:
+            self.shadow = {k: self._clone(q) for k, q in self.p.items()}
         self.last_sumsq: Optional[torch.Tensor] = None       # the device scalar the last step clipped with (sum of all squared gradients)
+
+    @staticmethod
+    def _clone(q):
+        """a second buffer with q's bits: a tensor, or a packed image copied as it lies (padding rows included)"""
+        if not isinstance(q, ops.PackedWeight):
+            return q.clone()
+        c = object.__new__(ops.PackedWeight)
+        c.N, c.K, c.dtype, c.data = q.N, q.K, q.dtype, q.data.clone()
+        return c
 
     def shapes(self) -> Dict[str, Tuple[int, ...]]:
         return member_shapes(self.C, self.D, self.H, self.F, self.T)
@@ -269,8 +291,13 @@ class NoiseEstimatorTrainer:
         for i, k in enumerate(PARAM_KEYS):
             ops.sumsq(g[k], acc, accumulate=i > 0)
         a = ops.adam_step(self.lr, self.t + 1, betas=self.betas, eps=self.eps)
-        for k in PARAM_KEYS:
-            ops.clip_adam(self.p[k], self.m[k], self.v[k], g[k], a, sumsq=acc, max_norm=self.grad_clip)
+        if self.shadow is None:
+            for k in PARAM_KEYS:
+                ops.clip_adam(self.p[k], self.m[k], self.v[k], g[k], a, sumsq=acc, max_norm=self.grad_clip)
+        else:                                                # EMA.update after optimizer.step() (:1006-1011), in the optimizer's own pass
+            e = ops.ema_step(self.ema_rate)
+            for k in PARAM_KEYS:
+                ops.clip_adam(self.p[k], self.m[k], self.v[k], g[k], a, sumsq=acc, max_norm=self.grad_clip, shadow=self.shadow[k], ema=e)
         self.t += 1                                          # counted once all 29 updates are enqueued
         self.batches_tracked += 1
         self.last_sumsq = acc
@@ -278,14 +305,28 @@ class NoiseEstimatorTrainer:
 
     # ---- state ------------------------------------------------------------------------------------------------------------------
     def tensors(self, which: str = "p") -> Dict[str, torch.Tensor]:
-        """The parameters ('p') or Adam's moments ('m', 'v') as row-major device tensors, lin1.lin.weight WITH its padded columns."""
-        src = {"p": self.p, "m": self.m, "v": self.v}[which]
+        """The parameters ('p'), Adam's moments ('m', 'v') or the EMA shadow ('ema', with a rate only) as row-major device tensors,
+        lin1.lin.weight WITH its padded columns."""
+        if which == "ema" and self.shadow is None:
+            raise ValueError("this trainer keeps no EMA shadow (ema_rate=None)")
+        src = {"p": self.p, "m": self.m, "v": self.v, "ema": self.shadow}[which]
         return {k: (q.unpack() if isinstance(q, ops.PackedWeight) else q.clone()) for k, q in src.items()}
 
     def state_dict(self, cpu: bool = True) -> Dict[str, torch.Tensor]:
         """ConditionalModel.state_dict(): the reference's keys and shapes, the running statistics and num_batches_tracked (int64)
         included -- what load_noise_estimators / EnsembleEngine.load_member read.  cpu=False keeps the tensors on the device."""
-        full = self.tensors("p")
+        return self._state_dict("p", cpu)
+
+    def ema_state_dict(self, cpu: bool = True) -> Dict[str, torch.Tensor]:
+        """What the reference's EMA.ema(model); model.state_dict() gives (:1498-1502): state_dict()'s keys, shapes and dtypes with the
+        SHADOW under the 29 parameter keys, and the LIVE running statistics and num_batches_tracked -- the reference's EMA walks
+        named_parameters() only, so the buffers are the model's own.  Needs a trainer built with ema_rate."""
+        if self.shadow is None:
+            raise ValueError("this trainer keeps no EMA shadow (ema_rate=None)")
+        return self._state_dict("ema", cpu)
+
+    def _state_dict(self, which: str, cpu: bool) -> Dict[str, torch.Tensor]:
+        full = self.tensors(which)
         full["lin1.lin.weight"] = full["lin1.lin.weight"][:, :2 * self.C].contiguous()
         sd: Dict[str, torch.Tensor] = {}
         for k in PARAM_KEYS:
@@ -299,14 +340,20 @@ class NoiseEstimatorTrainer:
 
     # ---- the whole training state, for snapshots (snapshot.py) ---------------------------------------------------------------------
     def _meta(self) -> dict:
+        ema = {} if self.ema_rate is None else {"ema_rate": self.ema_rate}
         return dict({"format": snapshot.FORMAT, "kind": "noise_estimator", "num_classes": self.C, "data_dim": self.D, "hidden_dim": self.H,
-                     "feature_dim": self.F, "timesteps": self.T}, **self.run_meta)
+                     "feature_dim": self.F, "timesteps": self.T}, **ema, **self.run_meta)
+
+    def _state_parts(self):
+        """(name in a snapshot, the dict of this trainer) of everything stored under the parameters' keys"""
+        parts = (("p", self.p), ("m", self.m), ("v", self.v))
+        return parts if self.shadow is None else parts + (("ema", self.shadow),)
 
     def training_state(self) -> dict:
         """Everything a continued run needs, on the CPU, row-major, in the reference's keys and shapes: {'meta', 'p', 'm', 'v' (Adam's
         moments under the parameters' keys; lin1.lin.weight cut to [F, 2C] in all three), 'buf' (the running statistics), 't',
-        'batches_tracked', 'lr'}.  One tensor is unpacked, copied out and released at a time: the device holds at most one row-major
-        weight beside the model."""
+        'batches_tracked', 'lr'}, and with an EMA rate 'ema' (the shadow, keys and shapes as 'p') and meta's 'ema_rate'.  One tensor
+        is unpacked, copied out and released at a time: the device holds at most one row-major weight beside the model."""
         def out(k, q):
             w = q.unpack() if isinstance(q, ops.PackedWeight) else q
             if k == "lin1.lin.weight":
@@ -314,7 +361,7 @@ class NoiseEstimatorTrainer:
             return w.detach().contiguous().cpu()
 
         state = {"meta": self._meta()}
-        for which, src in (("p", self.p), ("m", self.m), ("v", self.v)):
+        for which, src in self._state_parts():
             state[which] = {k: out(k, src[k]) for k in PARAM_KEYS}
         state["buf"] = {k: b.detach().cpu().clone() for k, b in self.buf.items()}
         state.update(t=int(self.t), batches_tracked=int(self.batches_tracked), lr=float(self.lr))
@@ -323,10 +370,15 @@ class NoiseEstimatorTrainer:
     def load_training_state(self, state: dict) -> None:
         """training_state() of a run with this run's meta (snapshot.check_meta: a ValueError names the field that differs), put back
         bit for bit: the packed images are rebuilt from the row-major tensors (PackedWeight: padding rows zero, as they were), one tensor
-        at a time.  Everything is checked before the first tensor of this trainer is replaced."""
+        at a time.  Everything is checked before the first tensor of this trainer is replaced.  The EMA shadow must be kept on both sides or
+        on neither, at one rate: a ValueError names ema_rate otherwise."""
         snapshot.check_meta(state.get("meta"), self._meta())
+        if self.ema_rate is None and "ema" in state:         # check_meta has refused a snapshot that records a rate; this one only holds a shadow
+            raise ValueError("ema_rate: the snapshot holds an EMA shadow ('ema'), this run keeps none (ema_rate=None)")
+        if self.ema_rate is not None and "ema" not in state:
+            raise ValueError("ema_rate: the snapshot records a rate and holds no 'ema' entry")
         shapes = self.shapes()
-        for which in ("p", "m", "v"):
+        for which, _ in self._state_parts():
             for k in PARAM_KEYS:
                 if k not in state[which]:
                     raise KeyError(f"the snapshot's '{which}' is missing '{k}'")
@@ -335,7 +387,7 @@ class NoiseEstimatorTrainer:
         for k, b in self.buf.items():
             if k not in state["buf"] or tuple(state["buf"][k].shape) != tuple(b.shape):
                 raise ValueError(f"buf['{k}'] is missing or has another shape than {tuple(b.shape)}")
-        for which, dst in (("p", self.p), ("m", self.m), ("v", self.v)):
+        for which, dst in self._state_parts():
             for k in PARAM_KEYS:
                 w = state[which][k].detach().to(self.device, torch.float32).contiguous()
                 if k == "lin1.lin.weight":
