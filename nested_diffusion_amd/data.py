@@ -310,6 +310,20 @@ class DeviceImageSet:
         return IndexBatchLoader(self, batch_size, shuffle=shuffle, generator=generator, drop_last=drop_last)
 
 
+def split_loader(root: str, split: str, dataset: str, preprocess: str, image_size, batch_size: int, cache: str = "none",
+                 flag: str = "cache", cache_dir=None, device=None, workers=None, num_workers: int = 0, **order):
+    """The training-time loader of <root>/<split>: a DataLoader over the ImageFolderDataset (num_workers processes), or with cache
+    'device' the same batches in the same order from a DeviceImageSet on `device` (default 'cuda'; decoded by `workers` threads, kept
+    in cache_file(cache_dir, split, ...)).  **order: shuffle, generator and drop_last, for either.  `flag` is the name the caller's
+    setting goes by in the refusal of a cache outside CACHE_CHOICES."""
+    if cache not in CACHE_CHOICES:
+        raise ValueError(f"{flag} must be one of {CACHE_CHOICES} ({flag}={cache!r})")
+    ds = ImageFolderDataset(os.path.join(root, split), dataset, preprocess, image_size)
+    if cache == "device":
+        return DeviceImageSet(ds, device or "cuda", workers=workers, cache_path=cache_file(cache_dir, split, ds)).loader(batch_size, **order)
+    return torch.utils.data.DataLoader(ds, batch_size=batch_size, num_workers=num_workers, **order)
+
+
 ATTACKS = ("FGSM", "PGD", "BIM", "AUTOPGD", "CW")
 ATTACKED_DATASETS = tuple(f"{d}Atk{a}" for d in ("ChestXRay", "ISICSkinCancer") for a in ATTACKS)   # diffusion/utils.py:165-177
 
@@ -343,7 +357,7 @@ def get_test_loader(args, config, shard=None):
         return SyntheticLoader(n, B, config.data.num_classes, seed=getattr(args, "seed", 0) or 0, size=size, shard=shard)
     ds = get_dataset(args, config)
     lo, hi = shard if shard is not None else (0, B)
-    # pinned batches: the runner uploads them with a non-blocking copy on a side stream (runner._rank_batches) without a staging copy
+    # pinned batches: the runner uploads them with a non-blocking copy on a side stream (upload.rank_batches) without a staging copy
     loader = torch.utils.data.DataLoader(ds, batch_sampler=ShardBatchSampler(len(ds), B, lo, hi),
                                          num_workers=int(getattr(config.data, "num_workers", 0) or 0), pin_memory=torch.cuda.is_available())
     loader.shard = (lo, hi) if shard is not None else None

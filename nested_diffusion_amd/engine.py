@@ -322,7 +322,7 @@ class EnsembleEngine:
     def enable_input_flag(self) -> None:
         """Ask the library to publish, per predict_batch call, the moment its input buffer has been read (nd_set_input_flag): a pinned
         host word receives the count of calls whose inputs are consumed -- about a quarter into the batch -- so a loader can refill
-        batch_buffers(...)['images'] for the next batch under this batch's sampler (runner._rank_batches)."""
+        batch_buffers(...)['images'] for the next batch under this batch's sampler (upload.rank_batches)."""
         if getattr(self, "_input_flag", None) is None:
             self._input_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
             self._batch_calls = 0

@@ -122,3 +122,56 @@ def random_crop_and_resize(images_in: torch.Tensor, k: float, corners=None) -> t
         corners = pick_crop_corners(B, W, k)
     c = torch.tensor(corners, dtype=torch.int32, device=x.device).reshape(B, 2).contiguous()
     return _resize(x, H, W, crop=c, crop_size=crop)
+
+
+# ---- the protocol's six flags (classification_train_separately.py:726-737), in the reference's order ------------------------------------
+def _noise(images, std, lo, hi, B_total):
+    z = torch.randn((B_total,) + tuple(images.shape[1:]), dtype=torch.float32, device=images.device)
+    return add_noise(images, std, z=z[lo:hi])
+
+
+def _covered(images, covered, lo, hi, B_total):
+    H, W = images.shape[-2:]
+    _, rects = pick_cover_regions(B_total, H, W, covered[0], int(covered[1]))
+    return random_cover_new(images, covered, rects=rects[lo:hi])
+
+
+def _crop(images, k, lo, hi, B_total):
+    corners = pick_crop_corners(B_total, images.shape[-1], k)
+    return random_crop_and_resize(images, k, corners=corners[lo:hi])
+
+
+# (flag, is the value active?, the step): the one table requested() and apply() read.  The steps name the kernel wrappers in their
+# bodies, so each is looked up in this module when it is called.
+FLAGS = (
+    ("noise_perturbation", lambda v: (v or 0.0) > 0.0, _noise),
+    ("low_resolution", lambda v: (v or 0) > 1, lambda images, k, lo, hi, B_total: down_up_sample(images, k)),
+    ("brightness", lambda v: (v or 0.0) != 0.0, lambda images, k, lo, hi, B_total: adjust_brightness(images, k)),
+    ("contrast", lambda v: v not in (1.0, None), lambda images, k, lo, hi, B_total: adjust_contrast(images, k)),
+    ("covered", lambda v: (v or (0.0, 0.0))[0] > 0, _covered),
+    ("crop", lambda v: (v or 0.0) > 0, _crop),
+)
+
+
+def requested(args) -> list:
+    """The perturbations the flags ask for, as [(flag, value)] in the order they are applied: those that change pixels on the device.
+    A flag that is absent, None or at its neutral value (0, contrast 1.0, low_resolution <= 1, covered[0] <= 0) asks for nothing."""
+    values = ((name, active, getattr(args, name, None)) for name, active, _ in FLAGS)
+    return [(name, v) for name, active, v in values if active(v)]
+
+
+def apply(args, images: torch.Tensor, lo: int = 0, hi: Optional[int] = None, B_total: Optional[int] = None) -> torch.Tensor:
+    """images: rows [lo, hi) of a test batch of B_total images (default: the whole batch), through requested(args).  Every rank holds
+    the same --seed (set_seed, :31-38) and makes the reference's RNG calls for the WHOLE batch in the reference's order -- the device
+    draw of add_noise (utils.py:274), python `random` for the cover rectangles (:321-343), torch.randint for the crop corners
+    (:296-300) -- and applies rows [lo, hi) of them to its own images: image i gets the same noise, windows and crops at
+    world 1, 2, 4, 8, and only the shard's pixels are ever moved or touched.  With nothing requested the tensor comes back as it is."""
+    n_local = images.shape[0]
+    hi = lo + n_local if hi is None else hi
+    B_total = n_local if B_total is None else B_total
+    if hi - lo != n_local or not (0 <= lo <= hi <= B_total):
+        raise ValueError(f"perturb: {n_local} rows for the shard [{lo}, {hi}) of {B_total}")
+    steps = {name: step for name, _, step in FLAGS}
+    for name, value in requested(args):
+        images = steps[name](images, value, lo, hi, B_total)
+    return images

@@ -2,7 +2,9 @@
 diffusion/classification_train_separately.py -- __init__ schedule block (:215-226), conditioner
 loading (:249-275), compute_guiding_prediction (:330-348), convert_to_prob (:392-398),
 compute_ensemble_confidence (:425-447), majority_voting_for_mc_samples (:51-68) and the hot loop
-of test_atk (:749-794), plus the report metrics and test_calibrate, and train (:842-1141) for one noise estimator.
+of test_atk (:749-794), plus the report metrics and test_calibrate.  Three jobs of the reference's class live in modules of
+their own and are only called from here: the rank's batch pipeline (upload.py), the robustness perturbations (perturb.py) and the
+training loop of one noise estimator, train (:842-1141; train_diffusion.py).
 
 Host code is PyTorch plumbing; every tensor operation of the hot path runs in libnd_hip.so.
 """
@@ -15,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import ops, snapshot
+from . import ops, perturb as P, upload
 from .diffusion_utils import SKIP_TYPES, sampler_plan, schedule_tables, timestep_sequence
 from .engine import EnsembleEngine
 from .mapping import GuidingConditioner, load_checkpoint_object, load_conditioner, require_fp32_split
@@ -221,156 +223,16 @@ class Diffusion(object):
     # ---- training of one noise estimator (:842-1141) ---------------------------------------------
     def train(self, mlp_idx: int, train_loader=None, valid_loader=None) -> dict:
         """Diffusion.train (:842-1141) for the noise estimator conditioned on mapping MLP `mlp_idx` (-1: on the full ViT's output), on ONE
-        GPU: per step the learning rate of lr_at (when optim.lr_schedule is set), the antithetic timestep draw, the conditioner's
-        softmax as yhat, e = randn, and one train_diffusion.NoiseEstimatorTrainer.step (q_sample, the model in train mode, the
-        mean-squared error, backward, clip_grad_norm_, Adam).  Every training.validation_freq epochs and on the last one the
-        validation set is sampled with the current weights on the FULL chain, with or without --sample_steps (p_sample_loop in eval mode: trainer.state_dict() loaded into a one-member
-        EnsembleEngine, noise drawn in the library) and the top-1 accuracy of y_0 taken; a new best writes
-        <log_path>/diffu{idx}_ckpt_best_eph{epoch}_acc{acc:.4f}.pth = {'noise_estimator', 'optimizer', 'epoch'}, the layout
-        load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: the best file is for inference, and Adam's moments of
-        the 150528 x 4096 layer would triple it.  The whole training state goes to <log_path>/ckpt.pth instead (the reference's
-        name, :890-908), every args.snapshot_epochs epochs and after the last: {'trainer': trainer.training_state(), 'loop':
-        {'next_epoch', 'step', 'max_accuracy', 'best', 'losses', 'accuracies'}, 'rng': snapshot.rng_state, the validation engine's
-        sampler state included}; args.resume_training continues from it at the top of epoch 'next_epoch' (a FileNotFoundError
-        names the file if there is none), with lr_at on the true epoch index, and returns the earlier epochs too.  args.ema
-        (main --ema) keeps the reference's EMA shadow of the parameters at config.model.ema_rate (a missing rate or one outside (0, 1) is
-        refused by name before anything is built): every step's optimizer pass updates it, the best file gains a fourth entry 'ema' =
-        trainer.ema_state_dict() (what --use_ema reads), ckpt.pth carries it and a resumed run restores it.  Validation and the choice of
-        the best epoch stay on the live weights, as in the reference: the losses, accuracies, best epochs and 'noise_estimator' bits
-        are those of a run without the flag.  Without it nothing is kept, whatever model.ema says in the config.  train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches
-        (default: <dataroot>/training shuffled in batches of training.batch_size, <dataroot>/validation in batches of
-        testing.batch_size, drop_last; with --train_cache device the same batches in the same order from data.DeviceImageSet, decoded once
-        and gathered on the GPU, --cache_dir keeping the decoded sets for later runs).  Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
-        from .train_diffusion import NoiseEstimatorTrainer, antithetic_timesteps, cast_label_to_one_hot_and_prototype, lr_at
-        args, config = self.args, self.config
-        K = len(self.cond_pred_model.mlps)
-        if not -1 <= mlp_idx < K:
-            raise NotImplementedError(f"mlp_idx must be -1 (the ViT's output) or in [0, {K}) (mlp_idx={mlp_idx})")
-        _, world = nd_dist.rank_world()
-        if world > 1:
-            raise NotImplementedError("Diffusion.train runs on one GPU: world size > 1 is not implemented")
-        if getattr(args, "train_guidance_only", False):
-            raise NotImplementedError("--train_guidance_only is not implemented")
-        if config.diffusion.aux_cls.arch != "sevit":
-            raise NotImplementedError(f"aux_cls.arch == {config.diffusion.aux_cls.arch!r}: only 'sevit' is implemented")
-        if self.operand_dtype != "f32":
-            raise NotImplementedError("training runs in fp32 mode: the fp16 mode is not implemented")
-        # --resume_training: the snapshot is read before anything is built, so a missing file costs nothing
-        snap_path = os.path.join(args.log_path, "ckpt.pth")                   # the reference's file name (:890-908, commented out there)
-        snapshot_epochs = int(getattr(args, "snapshot_epochs", 0) or 0)
-        snap = snapshot.read(snap_path) if getattr(args, "resume_training", False) else None
-        ema_rate = None
-        if getattr(args, "ema", False):
-            ema_rate = getattr(config.model, "ema_rate", None)
-            if isinstance(ema_rate, bool) or not isinstance(ema_rate, (int, float)) or not 0.0 < float(ema_rate) < 1.0:
-                raise ValueError(f"model.ema_rate: --ema needs a rate in (0, 1) in the config (model.ema_rate={ema_rate!r})")
-        print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
-        B_valid = config.testing.batch_size
-        if train_loader is None or valid_loader is None:
-            from .data import CACHE_CHOICES, DeviceImageSet, ImageFolderDataset, cache_file
-            workers = int(getattr(config.data, "num_workers", 0) or 0)
-            cache, cache_dir = getattr(args, "train_cache", None) or "none", getattr(args, "cache_dir", None)
-            if cache not in CACHE_CHOICES:
-                raise ValueError(f"train_cache must be one of {CACHE_CHOICES} (train_cache={cache!r})")
-            side = int(round((config.model.data_dim / 3) ** 0.5))          # 224 for data_dim = 150528 (3 x 224 x 224)
-            size = (side, side) if 3 * side * side == config.model.data_dim else (224, 224)
-
-            def loader(split, batch_size, **kw):
-                """the DataLoader of the split, or with --train_cache device the same batches from a device-resident set"""
-                ds = ImageFolderDataset(os.path.join(config.data.dataroot, split), config.data.dataset, args.preprocess, size)
-                if cache == "device":
-                    return DeviceImageSet(ds, self.device, cache_path=cache_file(cache_dir, split, ds)).loader(batch_size, **kw)
-                return torch.utils.data.DataLoader(ds, batch_size=batch_size, num_workers=workers, **kw)
-
-            if train_loader is None:
-                train_loader = loader("training", config.training.batch_size, shuffle=True)
-            if valid_loader is None:
-                valid_loader = loader("validation", B_valid, shuffle=False, drop_last=True)
-        trainer = NoiseEstimatorTrainer(config, self.device, seed=self.seed or 0, ema_rate=ema_rate)
-        self.trainer = trainer                     # stays reachable after the run: its training_state() is what a snapshot holds
-        batch_size = snapshot.loader_batch_size(train_loader)
-        trainer.run_meta = {"mlp_idx": int(mlp_idx), "dataset": config.data.dataset, "train_batches": len(train_loader),
-                            "batch_size": config.training.batch_size if batch_size is None else batch_size,
-                            "epochs": int(config.training.n_epochs)}
-        engine: Optional[EnsembleEngine] = None
-        n_epochs, freq = config.training.n_epochs, config.training.validation_freq
-        log_freq = getattr(config.training, "logging_freq", 0) or 0
-        max_accuracy, step, best, first_epoch = 0.0, 0, None, 0
-        losses, accuracies = [], {}
-
-        def yhat_of(images):
-            logits = self.compute_guiding_prediction(images, include_full_vit=mlp_idx == -1)
-            return ops.softmax_rows(logits[mlp_idx].contiguous())            # :955-958
-
-        def validation_engine():
-            eng = EnsembleEngine(config.data.num_classes, config.model.data_dim, config.model.hidden_dim, config.model.feature_dim,
-                                 self.num_timesteps, n_members=1, max_batch=B_valid, max_rows=B_valid, device=self.device)
-            eng.set_schedule(self.alphas, self.one_minus_alphas_bar_sqrt)
-            eng.seed(self.seed or 0)
-            return eng
-
-        if snap is not None:
-            trainer.load_training_state(snap["trainer"])
-            loop = snap["loop"]
-            first_epoch, step, max_accuracy, best = int(loop["next_epoch"]), int(loop["step"]), float(loop["max_accuracy"]), loop["best"]
-            losses, accuracies = [float(v) for v in loop["losses"]], {int(k): float(v) for k, v in loop["accuracies"].items()}
-            if snap["rng"].get("engine") is not None:                        # the run had validated: its sampler state goes back
-                engine = validation_engine()
-            snapshot.set_rng_state(snap["rng"], self.device, train_loader, engine)
-            snap = None
-            logging.info(f"Resumed from {snap_path} at epoch {first_epoch}, step {step}")
-        for epoch in range(first_epoch, n_epochs):
-            loss = None
-            for i, (x_raw, labels) in enumerate(train_loader):
-                x = x_raw.to(self.device, torch.float32).contiguous()
-                y0, _ = cast_label_to_one_hot_and_prototype(labels, config, return_prototype=False)
-                if config.optim.lr_schedule:
-                    trainer.lr = lr_at(i / len(train_loader) + epoch, config)     # :927-928
-                n = x.shape[0]
-                step += 1
-                t = antithetic_timesteps(n, self.num_timesteps)                   # :945-948, on the CPU
-                yhat = yhat_of(x)
-                e = torch.randn(n, config.data.num_classes, dtype=torch.float32, device=self.device)    # :965
-                loss, _ = trainer.step(torch.flatten(x, 1), y0.to(self.device), yhat, t, e)
-                if log_freq and (step % log_freq == 0 or step == 1):
-                    logging.info(f"During epoch: {epoch}, step: {step}, Noise Estimation loss: {loss.item()}")
-            if loss is None:
-                raise ValueError("the training loader is empty")
-            losses.append(float(loss))
-            logging.info(f"epoch: {epoch}, step: {step}, Noise Estimation loss: {losses[-1]}")
-            if epoch % freq == 0 or epoch + 1 == n_epochs:                        # :1054-1055
-                if engine is None:
-                    engine = validation_engine()
-                engine.load_member(0, trainer.state_dict(cpu=False))
-                acc_sum, n_batches = 0.0, 0
-                for images_raw, target in valid_loader:
-                    images = images_raw.to(self.device, torch.float32).contiguous()
-                    yhat = yhat_of(images)
-                    engine.encode(torch.flatten(images, 1))
-                    y_0 = engine.sample(yhat[None], yhat[None], None, mc=1, T=self.num_timesteps, use_graph=False)[0]   # :1103-1108
-                    acc_sum += float((y_0.argmax(dim=1).cpu() == target.cpu()).float().mean()) * 100.0    # accuracy in %, :1110
-                    n_batches += 1
-                if n_batches == 0:
-                    raise ValueError("the validation loader is empty")
-                acc_avg = acc_sum / n_batches
-                accuracies[epoch] = acc_avg
-                if acc_avg > max_accuracy:
-                    logging.info("Update accuracy at Epoch {}.".format(epoch))
-                    states = {'noise_estimator': trainer.state_dict(), 'optimizer': {'step': trainer.t, 'lr': trainer.lr}, 'epoch': epoch}
-                    if ema_rate is not None:
-                        states['ema'] = trainer.ema_state_dict()
-                    best = os.path.join(args.log_path, "diffu{}_ckpt_best_eph{}_acc{:.4f}.pth".format(mlp_idx, epoch, acc_avg))
-                    torch.save(states, best)
-                    print("Saved diffusion model {} at {}".format(mlp_idx, best))
-                max_accuracy = max(max_accuracy, acc_avg)
-                logging.info(f"epoch: {epoch}, step: {step}, Average diffusion {mlp_idx} accuracy: {acc_avg}%, "
-                             f"Max diffusion {mlp_idx} accuracy: {max_accuracy:.2f}%, ")
-            if snapshot.due(epoch, n_epochs, snapshot_epochs):
-                loop = {"next_epoch": epoch + 1, "step": step, "max_accuracy": max_accuracy, "best": best, "losses": list(losses),
-                        "accuracies": dict(accuracies)}
-                snapshot.atomic_save({"trainer": trainer.training_state(), "loop": loop,
-                                      "rng": snapshot.rng_state(self.device, train_loader, engine)}, snap_path)
-        return {"losses": losses, "accuracies": accuracies, "best": best}
+        GPU: train_diffusion.train_request refuses before anything is built, train_diffusion.train_noise_estimator is the loop (its
+        docstring says what a step, a validation, the best file, ckpt.pth and --ema are), with this runner's conditioner, schedule and
+        seed.  The trainer stays reachable as self.trainer, also when the run is cut: its training_state() is what a snapshot holds.
+        Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
+        from . import train_diffusion as td
+        request = td.train_request(self.args, self.config, mlp_idx, len(self.cond_pred_model.mlps), self.operand_dtype)
+        return td.train_noise_estimator(request, self.args, self.config, self.device, guide=self.compute_guiding_prediction,
+                                        alphas=self.alphas, one_minus_alphas_bar_sqrt=self.one_minus_alphas_bar_sqrt, seed=self.seed or 0,
+                                        train_loader=train_loader, valid_loader=valid_loader,
+                                        built=lambda trainer: setattr(self, "trainer", trainer))
 
     # ---- the hot path (:749-794) --------------------------------------------------------------
     @torch.no_grad()
@@ -405,123 +267,19 @@ class Diffusion(object):
         return z[:, :, :, lo:hi].reshape(K, T, mc * (hi - lo), C).contiguous()
 
     def _perturbs(self) -> bool:
-        """Does any flag of the robustness protocol change the pixels on the device (perturb: :726-737)?"""
-        a = self.args
-        covered = getattr(a, "covered", (0.0, 0.0)) or (0.0, 0.0)
-        return bool((getattr(a, "noise_perturbation", 0.0) or 0.0) > 0.0 or (getattr(a, "low_resolution", 0) or 0) > 1
-                    or (getattr(a, "brightness", 0.0) or 0.0) != 0.0 or getattr(a, "contrast", 1.0) not in (1.0, None)
-                    or covered[0] > 0 or (getattr(a, "crop", 0.0) or 0.0) > 0)
+        """Does any flag of the robustness protocol change the pixels on the device (perturb.requested: :726-737)?"""
+        return bool(P.requested(self.args))
 
     def _rank_batches(self, test_loader, lo: int, hi: int, B_total: int):
         """The rank's slice of every batch of the loader, on the device: yields (images [hi-lo, 3, S, S] perturbed, targets [hi-lo]).
-        A loader that is already sharded (data.get_test_loader(shard=...): its .shard attribute) hands over the rank's rows only -- only
-        those files were decoded; a full-batch loader (the reference's, or a caller's) is sliced on the HOST.  The slice is pinned
-        (as handed over, or through a staging buffer) and copied on a side stream, never on the compute stream
-        (classification_train_separately.py:722 is a blocking .to(device) of the whole batch on the compute stream):
-          * no device-side perturbation configured: STRAIGHT into the library's input buffer, as soon as the previous batch's graph has
-            read that buffer (nd_set_input_flag: about a quarter into the batch) -- the transfer runs beside the previous batch's sampler,
-            with no staging buffer on the device and no device-to-device copy;
-          * otherwise: into one of two device buffers one batch ahead (perturb then makes new tensors out of it)."""
-        main = torch.cuda.current_stream(self.device)
-        side = torch.cuda.Stream(self.device)
-        sharded = getattr(test_loader, "shard", None) == (lo, hi)
-        pins, bufs, evs, held = [None, None], [None, None], [None, None], [None, None]
-        tpins, tbufs = [None, None], [None, None]
+        upload.rank_batches is the pipeline (pinned staging, a side stream, straight into the library's input buffer when nothing
+        perturbs or attacks the batch on the device); this runner's engine, perturb and bytes_uploaded are what it works on."""
+        def count(n):
+            self.bytes_uploaded += n
 
-        def rows_of(item):
-            images_raw, target = item
-            x = images_raw if sharded else images_raw[lo:hi]
-            t = target if sharded else target[lo:hi]
-            if x.shape[0] != hi - lo:
-                raise ValueError(f"loader handed {x.shape[0]} rows for the shard [{lo}, {hi})")
-            return x, t
-
-        def host_stage(k, x, t):
-            """pinned source of the batch's H2D copy (the tensor itself if the loader pinned it) and of its targets"""
-            if evs[k] is not None:
-                evs[k].synchronize()                        # the copy that last read staging buffer k (two batches ago)
-            if x.dtype == torch.float32 and x.is_pinned():  # a loader with pin_memory=True: nothing to stage
-                src = x
-            else:
-                if pins[k] is None or pins[k].shape != x.shape:
-                    pins[k] = torch.empty(x.shape, dtype=torch.float32, pin_memory=True)
-                if x.dtype == torch.float32 and x.is_contiguous():
-                    # one memcpy on this thread.  (Tensor.copy_ spreads a 19 MB copy over every logical CPU the box shows; under a
-                    # container's CPU quota that takes 20-60 ms instead of 2 -- measured: bench.py's pcie_inclusive leg)
-                    import numpy as np
-                    np.copyto(pins[k].numpy(), x.numpy())
-                else:
-                    pins[k].copy_(x)
-                src = pins[k]
-            # the targets ride along (pinned too: a pageable H2D copy on the compute stream would hold the HOST until the running batch
-            # has finished, and the launches behind it would start late)
-            if tpins[k] is None or tpins[k].shape != t.shape or tpins[k].dtype != t.dtype:
-                tpins[k] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-                tbufs[k] = torch.empty(t.shape, dtype=t.dtype, device=self.device)
-            tpins[k].copy_(t)
-            held[k] = src                                   # a caller's pinned batch stays alive until its copy has been waited for
-            return src
-
-        first = None
-        it = iter(test_loader)
-        for first in it:
-            break
-        if first is None:
-            return
-        x0, _ = rows_of(first)
-        direct = (not x0.is_cuda) and not self._perturbs() and self.engine is not None and x0.dim() == 4 \
-            and getattr(self, "_attack", None) is None                      # an attack reads the batch while the next one uploads
-        if direct:
-            eng = self.engine
-            eng.enable_input_flag()
-            fixed = eng.batch_buffers(hi - lo, self.mc_trials, self.sample_steps, tuple(x0.shape[1:]))["images"]
-            k, item = 0, first
-            while item is not None:
-                x, t = rows_of(item)
-                src = host_stage(k, x, t)
-                eng.inputs_consumed()                       # every batch launched so far has read `fixed`
-                with torch.cuda.stream(side):
-                    fixed.copy_(src, non_blocking=True)
-                    tbufs[k].copy_(tpins[k], non_blocking=True)
-                    evs[k] = torch.cuda.Event()
-                    evs[k].record(side)
-                main.wait_event(evs[k])
-                self.bytes_uploaded += x.numel() * 4
-                tdev = tbufs[k]
-                k ^= 1
-                yield fixed, tdev
-                item = next(it, None)
-            return
-
-        def stage(k, item):
-            x, t = rows_of(item)
-            if x.is_cuda:                                   # a caller's loader that already lives on the device
-                return x.to(self.device, torch.float32), t.to(self.device), None
-            if bufs[k] is None or bufs[k].shape != x.shape:
-                bufs[k] = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-            src = host_stage(k, x, t)
-            side.wait_stream(main)                          # bufs[k]'s last reader (batch n - 1, already enqueued) before it is overwritten
-            with torch.cuda.stream(side):
-                bufs[k].copy_(src, non_blocking=True)
-                tbufs[k].copy_(tpins[k], non_blocking=True)
-                evs[k] = torch.cuda.Event()
-                evs[k].record(side)
-            self.bytes_uploaded += x.numel() * 4
-            return bufs[k], tbufs[k], evs[k]
-
-        nxt = stage(0, first)
-        k = 1
-        for item in it:
-            cur, nxt = nxt, stage(k, item)
-            k ^= 1
-            yield self._finish_batch(cur, main, lo, hi, B_total)
-        yield self._finish_batch(nxt, main, lo, hi, B_total)
-
-    def _finish_batch(self, staged, main, lo, hi, B_total):
-        x, t, ev = staged
-        if ev is not None:
-            main.wait_event(ev)
-        return self.perturb(x, lo, hi, B_total), t
+        direct_ok = not self._perturbs() and getattr(self, "_attack", None) is None   # an attack reads the batch while the next one uploads
+        yield from upload.rank_batches(test_loader, lo, hi, B_total, device=self.device, engine=self.engine, direct_ok=direct_ok,
+                                       perturb=self.perturb, mc_trials=self.mc_trials, sample_steps=self.sample_steps, count=count)
 
     # ---- temperature calibration (:449-629, driven by main.py:356-361) ---------------------------
     def test_calibrate(self, temp=None, test_loader=None):
@@ -562,36 +320,9 @@ class Diffusion(object):
 
     # ---- input perturbations (:726-737), in the reference's order ------------------------------
     def perturb(self, images_224: torch.Tensor, lo: int = 0, hi: Optional[int] = None, B_total: Optional[int] = None) -> torch.Tensor:
-        """images_224: rows [lo, hi) of a test batch of B_total images (default: the whole batch).  Every rank holds the same
-        --seed (set_seed, :31-38) and makes the reference's RNG calls for the WHOLE batch in the reference's order -- the device
-        draw of add_noise (utils.py:274), python `random` for the cover rectangles (:321-343), torch.randint for the crop corners
-        (:296-300) -- and applies rows [lo, hi) of them to its own images: image i gets the same noise, windows and crops at
-        world 1, 2, 4, 8, and only the shard's pixels are ever moved or touched."""
-        from . import perturb as P
-        a = self.args
-        n_local = images_224.shape[0]
-        hi = lo + n_local if hi is None else hi
-        B_total = n_local if B_total is None else B_total
-        if hi - lo != n_local or not (0 <= lo <= hi <= B_total):
-            raise ValueError(f"perturb: {n_local} rows for the shard [{lo}, {hi}) of {B_total}")
-        if (getattr(a, "noise_perturbation", 0.0) or 0.0) > 0.0:
-            z = torch.randn((B_total,) + tuple(images_224.shape[1:]), dtype=torch.float32, device=images_224.device)
-            images_224 = P.add_noise(images_224, a.noise_perturbation, z=z[lo:hi])
-        if (getattr(a, "low_resolution", 0) or 0) > 1:
-            images_224 = P.down_up_sample(images_224, a.low_resolution)
-        if (getattr(a, "brightness", 0.0) or 0.0) != 0.0:
-            images_224 = P.adjust_brightness(images_224, a.brightness)
-        if getattr(a, "contrast", 1.0) not in (1.0, None):
-            images_224 = P.adjust_contrast(images_224, a.contrast)
-        covered = getattr(a, "covered", (0.0, 0.0)) or (0.0, 0.0)
-        if covered[0] > 0:
-            H, W = images_224.shape[-2:]
-            _, rects = P.pick_cover_regions(B_total, H, W, covered[0], int(covered[1]))
-            images_224 = P.random_cover_new(images_224, covered, rects=rects[lo:hi])
-        if (getattr(a, "crop", 0.0) or 0.0) > 0:
-            corners = P.pick_crop_corners(B_total, images_224.shape[-1], a.crop)
-            images_224 = P.random_crop_and_resize(images_224, a.crop, corners=corners[lo:hi])
-        return images_224
+        """perturb.apply with this run's flags: rows [lo, hi) of a test batch of B_total images (default: the whole batch), the random
+        calls made for the WHOLE batch."""
+        return P.apply(self.args, images_224, lo, hi, B_total)
 
     # ---- test loop ----------------------------------------------------------------------------
     def test_atk(self, test_loader=None, attack=None):

@@ -54,10 +54,15 @@ def atomic_save(obj, path: str) -> None:
         raise
 
 
-def read(path: str) -> dict:
-    """The snapshot at `path`, on the CPU; a FileNotFoundError that names the path when there is none."""
+def require(path: str) -> None:
+    """A FileNotFoundError that names the path when there is no snapshot at `path`: what a loop asks before it builds anything."""
     if not os.path.isfile(path):
         raise FileNotFoundError(f"cannot resume: there is no snapshot at {path}")
+
+
+def read(path: str) -> dict:
+    """The snapshot at `path`, on the CPU; require()'s FileNotFoundError when there is none."""
+    require(path)
     snap = torch.load(path, map_location="cpu", weights_only=True)
     for part in ("trainer", "loop", "rng"):
         if not isinstance(snap, dict) or part not in snap:
@@ -113,3 +118,19 @@ def set_rng_state(state: dict, device, train_loader, engine=None) -> None:
         gen.set_state(state["loader"])
     if engine is not None and state.get("engine") is not None:
         engine.set_rng_state(state["engine"])
+
+
+# ---- the run protocol of the epoch loops (_trainer.EpochTrainer._fit, train_diffusion.train_noise_estimator) -----------------------------
+def load_run(path: str, trainer) -> dict:
+    """Resume, first half: read(path) -- so a missing file is refused before the trainer is touched -- and
+    trainer.load_training_state(snap['trainer']).  Returns the snapshot: the loop takes its counters from snap['loop'] and, once it has
+    its training loader (and its validation engine, if it samples), calls set_rng_state(snap['rng'], ...)."""
+    snap = read(path)
+    trainer.load_training_state(snap["trainer"])
+    return snap
+
+
+def save_run(path: str, trainer, loop: dict, device, train_loader, engine=None) -> None:
+    """The file of the module docstring, written at the end of an epoch: the trainer's whole state, the loop's counters for the top of
+    the next epoch, and rng_state(device, train_loader, engine)."""
+    atomic_save({"trainer": trainer.training_state(), "loop": loop, "rng": rng_state(device, train_loader, engine)}, path)

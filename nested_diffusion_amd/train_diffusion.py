@@ -21,16 +21,23 @@ EMA.ema(model); model.state_dict() gives, and training_state() / load_training_s
 copy of the parameters on the device.  Without a rate nothing of it exists: the same launches, allocations and state keys as ever.
 The reference never reads its shadow back in training -- the checkpoint saves noise_estimator.state_dict() (:1120) -- so the shadow
 changes nothing else a run writes.  Out of scope: train_guidance_only, more than one GPU, the fp16 mode.  training_state() /
-load_training_state() carry a run across an interruption (snapshot.py; Diffusion.train writes and reads the file)."""
+load_training_state() carry a run across an interruption (snapshot.py; train_noise_estimator writes and reads the file).
+
+The loop around the step, train_noise_estimator (what runner.Diffusion.train runs): train_request refuses, validate samples the validation
+set with the current weights, save_best writes the inference checkpoint."""
 from __future__ import annotations
 
+import logging
 import math
+import os
 from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import ops, snapshot
+from . import dist as nd_dist, ops, snapshot
+from .data import split_loader
 from .diffusion_utils import schedule_tables
+from .engine import EnsembleEngine
 from .latent_model import LIN1_K, check_member_dims, member_shapes, pad_lin1
 
 
@@ -401,3 +408,171 @@ class NoiseEstimatorTrainer:
         for k, b in self.buf.items():
             b.copy_(state["buf"][k])
         self.t, self.batches_tracked, self.lr = int(state["t"]), int(state["batches_tracked"]), float(state["lr"])
+
+
+# ---- the training loop of one noise estimator (Diffusion.train, :842-1141) ---------------------------------------------------------------
+def train_request(args, config, mlp_idx: int, n_mlps: int, operand_dtype: str) -> dict:
+    """Everything train_noise_estimator refuses, before anything is built: an mlp_idx outside -1 (the noise estimator conditioned on the
+    full ViT's output) .. n_mlps - 1 (on that mapping MLP), more than one GPU, --train_guidance_only, another conditioner than 'sevit',
+    the fp16 mode; with args.resume_training a missing <log_path>/ckpt.pth (FileNotFoundError, so a missing file costs nothing); with
+    args.ema (main --ema) a config.model.ema_rate that is missing or outside (0, 1), refused by name.  Returns the run's settings:
+    {'mlp_idx', 'snap_path', 'snapshot_epochs', 'resume', 'ema_rate' (None without --ema, whatever model.ema says in the config)}."""
+    if not -1 <= mlp_idx < n_mlps:
+        raise NotImplementedError(f"mlp_idx must be -1 (the ViT's output) or in [0, {n_mlps}) (mlp_idx={mlp_idx})")
+    _, world = nd_dist.rank_world()
+    if world > 1:
+        raise NotImplementedError("Diffusion.train runs on one GPU: world size > 1 is not implemented")
+    if getattr(args, "train_guidance_only", False):
+        raise NotImplementedError("--train_guidance_only is not implemented")
+    if config.diffusion.aux_cls.arch != "sevit":
+        raise NotImplementedError(f"aux_cls.arch == {config.diffusion.aux_cls.arch!r}: only 'sevit' is implemented")
+    if operand_dtype != "f32":
+        raise NotImplementedError("training runs in fp32 mode: the fp16 mode is not implemented")
+    snap_path = os.path.join(args.log_path, "ckpt.pth")                   # the reference's file name (:890-908, commented out there)
+    resume = bool(getattr(args, "resume_training", False))
+    if resume:
+        snapshot.require(snap_path)
+    ema_rate = None
+    if getattr(args, "ema", False):
+        ema_rate = getattr(config.model, "ema_rate", None)
+        if isinstance(ema_rate, bool) or not isinstance(ema_rate, (int, float)) or not 0.0 < float(ema_rate) < 1.0:
+            raise ValueError(f"model.ema_rate: --ema needs a rate in (0, 1) in the config (model.ema_rate={ema_rate!r})")
+    return {"mlp_idx": mlp_idx, "snap_path": snap_path, "snapshot_epochs": int(getattr(args, "snapshot_epochs", 0) or 0), "resume": resume,
+            "ema_rate": ema_rate}
+
+
+def default_loader(args, config, device, split: str, batch_size: int, **order):
+    """data.split_loader of <dataroot>/<split> as the run's flags ask for it: a DataLoader with config.data.num_workers processes, or
+    with --train_cache device the same batches in the same order from data.DeviceImageSet, decoded once and gathered on the GPU
+    (--cache_dir keeps the decoded sets for later runs)."""
+    side = int(round((config.model.data_dim / 3) ** 0.5))          # 224 for data_dim = 150528 (3 x 224 x 224)
+    size = (side, side) if 3 * side * side == config.model.data_dim else (224, 224)
+    return split_loader(config.data.dataroot, split, config.data.dataset, args.preprocess, size, batch_size,
+                        cache=getattr(args, "train_cache", None) or "none", flag="train_cache", cache_dir=getattr(args, "cache_dir", None),
+                        device=device, num_workers=int(getattr(config.data, "num_workers", 0) or 0), **order)
+
+
+def validate(engine: EnsembleEngine, trainer: NoiseEstimatorTrainer, valid_loader, yhat_of, num_timesteps: int) -> float:
+    """The validation set sampled with the current LIVE weights on the FULL chain, with or without --sample_steps (p_sample_loop in eval
+    mode: trainer.state_dict() loaded into the one-member `engine`, noise drawn in the library): the top-1 accuracy of y_0 in %, averaged
+    over the batches (:1103-1110)."""
+    engine.load_member(0, trainer.state_dict(cpu=False))
+    acc_sum, n_batches = 0.0, 0
+    for images_raw, target in valid_loader:
+        images = images_raw.to(trainer.device, torch.float32).contiguous()
+        yhat = yhat_of(images)
+        engine.encode(torch.flatten(images, 1))
+        y_0 = engine.sample(yhat[None], yhat[None], None, mc=1, T=num_timesteps, use_graph=False)[0]   # :1103-1108
+        acc_sum += float((y_0.argmax(dim=1).cpu() == target.cpu()).float().mean()) * 100.0    # accuracy in %, :1110
+        n_batches += 1
+    if n_batches == 0:
+        raise ValueError("the validation loader is empty")
+    return acc_sum / n_batches
+
+
+def save_best(trainer: NoiseEstimatorTrainer, log_path: str, mlp_idx: int, epoch: int, acc: float) -> str:
+    """<log_path>/diffu{idx}_ckpt_best_eph{epoch}_acc{acc:.4f}.pth = {'noise_estimator', 'optimizer', 'epoch'}, the layout
+    load_noise_estimators reads.  'optimizer' holds {'step', 'lr'} only: the best file is for inference, and Adam's moments of the
+    150528 x 4096 layer would triple it (the whole training state goes to ckpt.pth instead).  A trainer that keeps an EMA shadow adds a
+    fourth entry 'ema' = trainer.ema_state_dict(), what --use_ema reads.  Returns the path."""
+    states = {'noise_estimator': trainer.state_dict(), 'optimizer': {'step': trainer.t, 'lr': trainer.lr}, 'epoch': epoch}
+    if trainer.ema_rate is not None:
+        states['ema'] = trainer.ema_state_dict()
+    best = os.path.join(log_path, "diffu{}_ckpt_best_eph{}_acc{:.4f}.pth".format(mlp_idx, epoch, acc))
+    torch.save(states, best)
+    print("Saved diffusion model {} at {}".format(mlp_idx, best))
+    return best
+
+
+def train_noise_estimator(request: dict, args, config, device, *, guide, alphas, one_minus_alphas_bar_sqrt, seed: int, train_loader=None,
+                          valid_loader=None, built=None) -> dict:
+    """Diffusion.train (:842-1141) for the noise estimator of train_request's `request`, on ONE GPU.  A step: the learning rate of lr_at
+    (when optim.lr_schedule is set), the antithetic timestep draw, the softmax of guide(images, include_full_vit)[mlp_idx] (the runner's
+    compute_guiding_prediction) as yhat, e = randn, and one NoiseEstimatorTrainer.step.  Every training.validation_freq epochs and on
+    the last one: validate, and on a new best accuracy save_best; validation and the choice of the best epoch stay on the live weights
+    with --ema too, as in the reference, so the losses, accuracies, best epochs and 'noise_estimator' bits are those of a run without
+    the flag, while every step's optimizer pass updates the shadow, ckpt.pth carries it and a resumed run restores it.
+    The whole training state goes to <log_path>/ckpt.pth (the reference's name, :890-908) every args.snapshot_epochs epochs and after
+    the last (snapshot.save_run): 'loop' = {'next_epoch', 'step', 'max_accuracy', 'best', 'losses', 'accuracies'}, 'rng' with the
+    validation engine's sampler state; args.resume_training continues from it at the top of epoch 'next_epoch', with lr_at on the true
+    epoch index, and returns the earlier epochs too.
+    train_loader / valid_loader: loaders of (images [B, 3, S, S], labels [B]) batches (default: default_loader of 'training', shuffled in
+    batches of training.batch_size, and of 'validation' in batches of testing.batch_size, drop_last).  built(trainer) is called as soon
+    as the trainer exists: it stays reachable when the run is cut.
+    Returns {'losses': per-epoch last loss, 'accuracies': {epoch: acc}, 'best': path or None}."""
+    mlp_idx, snap_path, num_timesteps = request["mlp_idx"], request["snap_path"], config.diffusion.timesteps
+    print('NOTE: TRAINING DIFFUSION MODEL FOR MLP {}'.format(mlp_idx) if mlp_idx >= 0 else 'NOTE: TRAINING DIFFUSION MODEL FOR ViT OUTPUT')
+    B_valid = config.testing.batch_size
+    if train_loader is None:
+        train_loader = default_loader(args, config, device, "training", config.training.batch_size, shuffle=True)
+    if valid_loader is None:
+        valid_loader = default_loader(args, config, device, "validation", B_valid, shuffle=False, drop_last=True)
+    trainer = NoiseEstimatorTrainer(config, device, seed=seed, ema_rate=request["ema_rate"])
+    if built is not None:
+        built(trainer)
+    batch_size = snapshot.loader_batch_size(train_loader)
+    trainer.run_meta = {"mlp_idx": int(mlp_idx), "dataset": config.data.dataset, "train_batches": len(train_loader),
+                        "batch_size": config.training.batch_size if batch_size is None else batch_size,
+                        "epochs": int(config.training.n_epochs)}
+    engine: Optional[EnsembleEngine] = None
+    n_epochs, freq = config.training.n_epochs, config.training.validation_freq
+    log_freq = getattr(config.training, "logging_freq", 0) or 0
+    max_accuracy, step, best, first_epoch = 0.0, 0, None, 0
+    losses, accuracies = [], {}
+
+    def yhat_of(images):
+        logits = guide(images, include_full_vit=mlp_idx == -1)
+        return ops.softmax_rows(logits[mlp_idx].contiguous())            # :955-958
+
+    def validation_engine():
+        eng = EnsembleEngine(config.data.num_classes, config.model.data_dim, config.model.hidden_dim, config.model.feature_dim,
+                             num_timesteps, n_members=1, max_batch=B_valid, max_rows=B_valid, device=device)
+        eng.set_schedule(alphas, one_minus_alphas_bar_sqrt)
+        eng.seed(seed)
+        return eng
+
+    if request["resume"]:
+        snap = snapshot.load_run(snap_path, trainer)
+        loop = snap["loop"]
+        first_epoch, step, max_accuracy, best = int(loop["next_epoch"]), int(loop["step"]), float(loop["max_accuracy"]), loop["best"]
+        losses, accuracies = [float(v) for v in loop["losses"]], {int(k): float(v) for k, v in loop["accuracies"].items()}
+        if snap["rng"].get("engine") is not None:                        # the run had validated: its sampler state goes back
+            engine = validation_engine()
+        snapshot.set_rng_state(snap["rng"], device, train_loader, engine)
+        del snap
+        logging.info(f"Resumed from {snap_path} at epoch {first_epoch}, step {step}")
+    for epoch in range(first_epoch, n_epochs):
+        loss = None
+        for i, (x_raw, labels) in enumerate(train_loader):
+            x = x_raw.to(device, torch.float32).contiguous()
+            y0, _ = cast_label_to_one_hot_and_prototype(labels, config, return_prototype=False)
+            if config.optim.lr_schedule:
+                trainer.lr = lr_at(i / len(train_loader) + epoch, config)     # :927-928
+            n = x.shape[0]
+            step += 1
+            t = antithetic_timesteps(n, num_timesteps)                        # :945-948, on the CPU
+            yhat = yhat_of(x)
+            e = torch.randn(n, config.data.num_classes, dtype=torch.float32, device=device)    # :965
+            loss, _ = trainer.step(torch.flatten(x, 1), y0.to(device), yhat, t, e)
+            if log_freq and (step % log_freq == 0 or step == 1):
+                logging.info(f"During epoch: {epoch}, step: {step}, Noise Estimation loss: {loss.item()}")
+        if loss is None:
+            raise ValueError("the training loader is empty")
+        losses.append(float(loss))
+        logging.info(f"epoch: {epoch}, step: {step}, Noise Estimation loss: {losses[-1]}")
+        if epoch % freq == 0 or epoch + 1 == n_epochs:                        # :1054-1055
+            if engine is None:
+                engine = validation_engine()
+            acc_avg = validate(engine, trainer, valid_loader, yhat_of, num_timesteps)
+            accuracies[epoch] = acc_avg
+            if acc_avg > max_accuracy:
+                logging.info("Update accuracy at Epoch {}.".format(epoch))
+                best = save_best(trainer, args.log_path, mlp_idx, epoch, acc_avg)
+            max_accuracy = max(max_accuracy, acc_avg)
+            logging.info(f"epoch: {epoch}, step: {step}, Average diffusion {mlp_idx} accuracy: {acc_avg}%, "
+                         f"Max diffusion {mlp_idx} accuracy: {max_accuracy:.2f}%, ")
+        if snapshot.due(epoch, n_epochs, request["snapshot_epochs"]):
+            loop = {"next_epoch": epoch + 1, "step": step, "max_accuracy": max_accuracy, "best": best, "losses": list(losses),
+                    "accuracies": dict(accuracies)}
+            snapshot.save_run(snap_path, trainer, loop, device, train_loader, engine)
+    return {"losses": losses, "accuracies": accuracies, "best": best}

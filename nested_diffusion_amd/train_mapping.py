@@ -20,19 +20,18 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _trainer, ops, snapshot
-from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
-from .data import CACHE_CHOICES, DeviceImageSet, ImageFolderDataset, cache_file
+from ._trainer import (TRAIN_DIR, VALID_BATCH, VALID_DIR, EpochTrainer, add_cache_flags, add_snapshot_flags,  # noqa: F401  (this module's interface)
+                       cache_settings, make_loaders, snapshot_settings, step_lr)
+from .data import cache_file  # noqa: F401  (part of this module's interface)
 from .mapping import Classifier, VisionTransformer, load_pickled
 
 MAX_BATCH = ops.LINEAR_BWD_MAX_M      # rows per training step: one nd_linear_bwd / nd_linear_wgrad_adam launch
-VALID_BATCH = 70                      # mapping/data/dataset.py:271: the validation loader's batch
 
 # mapping/train_mapping.py:46-85 (the two datasets this package has a loader for)
 DATASET_DEFAULTS = {
     "ChestXRay": dict(num_classes=2, batch_size=30, lr=1e-3, step_size=20, gamma=0.5, epochs=301),
     "ISICSkinCancer": dict(num_classes=2, batch_size=30, lr=5e-4, step_size=20, gamma=0.5, epochs=100),
 }
-TRAIN_DIR, VALID_DIR = "training", "validation"   # mapping/data/dataset.py:13: data_loader's defaults
 
 
 class MappingTrainer(EpochTrainer):
@@ -187,62 +186,6 @@ def build_parser() -> argparse.ArgumentParser:
 def resolve_settings(args) -> dict:
     """The run's hyper-parameters: the per-dataset defaults with --epochs / --batch_size (at most MAX_BATCH) / --seed applied."""
     return _trainer.resolve_settings(args, DATASET_DEFAULTS, MAX_BATCH)
-
-
-def add_cache_flags(ap: argparse.ArgumentParser) -> None:
-    """--cache / --cache_dir / --workers: the training input of train_mapping and train_transformer.  A flag that is not given leaves no
-    attribute behind (the namespace of a run without them is what it was); cache_settings reads them with their defaults."""
-    ap.add_argument("--cache", default=argparse.SUPPRESS, choices=list(CACHE_CHOICES),
-                    help="'device': decode every image once, keep both splits on the GPU as bytes and gather each batch there "
-                         "(data.DeviceImageSet; same batches, same weights); 'none' (default): a DataLoader decodes every epoch")
-    ap.add_argument("--cache_dir", default=argparse.SUPPRESS, help="with --cache device: keep the decoded sets in this directory and reuse them in later runs")
-    ap.add_argument("--workers", type=int, default=argparse.SUPPRESS,
-                    help="with --cache device: decode threads, at most 16 (default: the CPUs this process may use, at most 16)")
-
-
-def add_snapshot_flags(ap: argparse.ArgumentParser, where: str) -> None:
-    """--snapshot_epochs / --resume of train_mapping and train_transformer; like the cache flags, a flag that is not given leaves no
-    attribute behind."""
-    ap.add_argument("--snapshot_epochs", type=int, default=argparse.SUPPRESS,
-                    help=f"write the whole training state (weights, Adam's moments, counters, generators) to {where} every N epochs and "
-                         f"after the last one (default 0: never)")
-    ap.add_argument("--resume", action="store_true", default=argparse.SUPPRESS,
-                    help=f"continue the run whose state is in {where} (weights, counters and the shuffle's position come from it): same dataset and batch size; --epochs may be larger")
-
-
-def snapshot_settings(args) -> dict:
-    """fit's snapshot_epochs / resume from a parsed command line: 0 and False unless given."""
-    n = int(getattr(args, "snapshot_epochs", 0))
-    if n < 0:
-        raise SystemExit(f"--snapshot_epochs must be at least 0 (got {n})")
-    return dict(snapshot_epochs=n, resume=bool(getattr(args, "resume", False)))
-
-
-def cache_settings(args) -> dict:
-    """make_loaders' cache / cache_dir / workers from a parsed command line: 'none', None, None unless given."""
-    return dict(cache=getattr(args, "cache", "none"), cache_dir=getattr(args, "cache_dir", None), workers=getattr(args, "workers", None))
-
-
-def make_loaders(root_dir: str, dataset: str, preprocess: str, batch_size: int, seed: int, cache: str = "none", cache_dir: Optional[str] = None,
-                 workers: Optional[int] = None, device=None, image_size=(224, 224)):
-    """(training loader, shuffled under the seed; validation loader, batches of VALID_BATCH in file order).  Unlike the reference's validation
-    loader (drop_last=True) the last partial batch is KEPT: the reference divides by the full dataset length either way, so on a set whose
-    size is no multiple of 70 its reported validation accuracy leaves the tail out of the numerator; here every image counts.  The
-    accuracy, and with it the epoch whose weights are saved, can therefore differ from the reference's on such a set.
-    cache='device': the same batches in the same order from data.DeviceImageSet (decoded once by `workers` threads, held on `device`,
-    default 'cuda'; images arrive on the device, labels on the CPU); cache_dir keeps the decoded sets as
-    <cache_dir>/<split>_<preprocess>_<H>x<W>.npz for later runs."""
-    if cache not in CACHE_CHOICES:
-        raise ValueError(f"cache must be one of {CACHE_CHOICES} (cache={cache!r})")
-    train = ImageFolderDataset(os.path.join(root_dir, TRAIN_DIR), dataset, preprocess, image_size)
-    valid = ImageFolderDataset(os.path.join(root_dir, VALID_DIR), dataset, preprocess, image_size)
-    g = torch.Generator().manual_seed(int(seed))
-    if cache == "device":
-        sets = [DeviceImageSet(ds, device or "cuda", workers=workers, cache_path=cache_file(cache_dir, split, ds))
-                for split, ds in ((TRAIN_DIR, train), (VALID_DIR, valid))]
-        return sets[0].loader(batch_size, shuffle=True, generator=g), sets[1].loader(VALID_BATCH, shuffle=False)
-    return (torch.utils.data.DataLoader(train, batch_size=batch_size, shuffle=True, generator=g),
-            torch.utils.data.DataLoader(valid, batch_size=VALID_BATCH, shuffle=False))
 
 
 def main(argv=None) -> dict:

@@ -24,9 +24,9 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _trainer, ops, snapshot
-from ._trainer import EpochTrainer, step_lr  # noqa: F401  (step_lr: part of this module's interface)
+from ._trainer import (TRAIN_DIR, VALID_DIR, EpochTrainer, add_cache_flags, add_snapshot_flags, cache_settings, make_loaders, snapshot_settings,
+                       step_lr)  # noqa: F401  (step_lr, make_loaders: part of this module's interface)
 from .mapping import LN_EPS, VisionTransformer, load_pickled, require_fp32_split
-from .train_mapping import TRAIN_DIR, VALID_DIR, add_cache_flags, add_snapshot_flags, cache_settings, make_loaders, snapshot_settings
 
 # mapping/train_transformer.py:47-49, 95-97 (the two datasets this package has a loader for)
 DATASET_DEFAULTS = {

@@ -187,3 +187,44 @@ def test_loader_path_selection_follows_the_perturbation_flags():
     assert not Diffusion._perturbs(ns(args=ns(**{**neutral, "low_resolution": 1, "covered": (0.0, 3.0)})))
     for k, v in (("noise_perturbation", 0.05), ("low_resolution", 2), ("brightness", -0.2), ("contrast", 0.8), ("covered", (0.1, 2.0)), ("crop", 0.25)):
         assert Diffusion._perturbs(ns(args=ns(**{**neutral, k: v}))), k
+
+
+def test_requested_and_apply_read_one_table_of_the_six_flags(monkeypatch):
+    """perturb.requested (what selects the loader loop's path, through Diffusion._perturbs) and perturb.apply (what changes the pixels)
+    cannot disagree: for each flag alone `requested` names exactly that flag and `apply` calls exactly its kernel wrapper once; with all
+    six on the wrappers run in the reference's order (:726-737); with nothing requested `apply` hands back the very tensor it was given.
+    The six wrappers are recorders here: no GPU."""
+    import argparse
+    import torch
+    from nested_diffusion_amd import perturb as P
+    from nested_diffusion_amd.runner import Diffusion
+    ns = argparse.Namespace
+    calls = []
+    wrappers = {"noise_perturbation": "add_noise", "low_resolution": "down_up_sample", "brightness": "adjust_brightness",
+                "contrast": "adjust_contrast", "covered": "random_cover_new", "crop": "random_crop_and_resize"}
+    for flag, fn in wrappers.items():
+        monkeypatch.setattr(P, fn, lambda x, value, *a, _flag=flag, **kw: (calls.append((_flag, value)), x.clone())[1])
+    neutral = dict(noise_perturbation=0.0, low_resolution=0, brightness=0.0, contrast=1.0, covered=None, crop=0.0)
+    active = dict(noise_perturbation=0.05, low_resolution=2, brightness=-0.2, contrast=0.8, covered=(0.1, 2.0), crop=0.25)
+    assert list(active) == list(wrappers) == [name for name, _, _ in P.FLAGS]
+    x = torch.zeros(4, 3, 8, 8)
+
+    def run(args):
+        del calls[:]
+        req, out = P.requested(args), P.apply(args, x)
+        assert Diffusion._perturbs(ns(args=args)) == bool(req)
+        assert Diffusion.perturb(ns(args=args), x) is x if not req else True
+        return req, out, list(calls)
+
+    for k, v in active.items():
+        req, out, seen = run(ns(**{**neutral, k: v}))
+        assert req == [(k, v)] and seen == [(k, v)] and out is not x, k
+        req, out, seen = run(ns(**{k: v}))                                          # the other five absent altogether
+        assert req == [(k, v)] and seen == [(k, v)], k
+    req, out, seen = run(ns(**active))
+    assert req == list(active.items()) and seen == list(active.items())
+    for quiet in (ns(**neutral), ns(), ns(**{**neutral, "low_resolution": 1, "covered": (0.0, 3.0)})):
+        req, out, seen = run(quiet)
+        assert req == [] and seen == [] and out is x
+    with pytest.raises(ValueError, match=r"perturb: 4 rows for the shard \[2, 5\) of 8"):
+        P.apply(ns(**active), x, 2, 5, 8)

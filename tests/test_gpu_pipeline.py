@@ -67,14 +67,8 @@ def test_conditioner_arena_poisoned_with_nans_changes_no_bit():
         assert torch.equal(a, b)
 
 
-def test_loader_loop_uploads_straight_into_the_input_buffer_and_matches_per_batch_calls():
-    """runner._rank_batches without device-side perturbations: every host batch is copied on a side stream STRAIGHT into the library's
-    input buffer as soon as the previous batch's graph has read it (nd_set_input_flag: a count published to pinned host memory right
-    behind the last kernel that reads the images), i.e. while the previous batch's sampler is still running.  Five DISTINCT batches
-    through test_atk must give exactly the probabilities of five plain predict_batch calls on explicitly uploaded tensors (same seed,
-    same in-library noise sequence): a refill that came too early would corrupt the batch still in flight, one that came too late or
-    skipped the wait for its own copy would feed stale pixels.  Also: the flag has counted every batch, only host bytes of the five
-    batches crossed PCIe, and with a perturbation flag on the loop takes the staged path and still agrees with per-batch calls."""
+def loader_loop_case():
+    """The small runner of the two loader-loop tests: (make(**flags) -> a fresh Diffusion, five distinct host batches, B, img, C)."""
     import argparse
     from nested_diffusion_amd.mapping import Classifier, GuidingConditioner, VisionTransformer
     from nested_diffusion_amd.runner import Diffusion
@@ -96,6 +90,18 @@ def test_loader_loop_uploads_straight_into_the_input_buffer_and_matches_per_batc
         cond = GuidingConditioner(VisionTransformer(vp, heads, "cuda"), [Classifier(m, "cuda") for m in mlps])
         return Diffusion(ns(seed=5, mc_trials=2, **flags), cfg, device="cuda", conditioner=cond, noise_estimator_states=[dict(m) for m in members])
 
+    return make, batches, B, img, C
+
+
+def test_loader_loop_uploads_straight_into_the_input_buffer_and_matches_per_batch_calls():
+    """runner._rank_batches without device-side perturbations: every host batch is copied on a side stream STRAIGHT into the library's
+    input buffer as soon as the previous batch's graph has read it (nd_set_input_flag: a count published to pinned host memory right
+    behind the last kernel that reads the images), i.e. while the previous batch's sampler is still running.  Five DISTINCT batches
+    through test_atk must give exactly the probabilities of five plain predict_batch calls on explicitly uploaded tensors (same seed,
+    same in-library noise sequence): a refill that came too early would corrupt the batch still in flight, one that came too late or
+    skipped the wait for its own copy would feed stale pixels.  Also: the flag has counted every batch, only host bytes of the five
+    batches crossed PCIe, and with a perturbation flag on the loop takes the staged path and still agrees with per-batch calls."""
+    make, batches, B, img, C = loader_loop_case()
     for flags in ({}, {"brightness": 0.1}):
         loop = make(**flags)
         loop.test_atk(test_loader=batches)
@@ -112,6 +118,44 @@ def test_loader_loop_uploads_straight_into_the_input_buffer_and_matches_per_batc
         want = torch.cat([plain.predict_batch(plain.perturb(x.cuda()))["prob"] for x, _ in batches])
         assert torch.equal(loop.last_probs, want), flags
         assert not torch.equal(want[:B], want[B:2 * B])                               # the batches really differ
+
+
+@pytest.mark.parametrize("flags", [{}, {"brightness": 0.1}], ids=["direct", "staged"])
+def test_loader_loop_takes_every_kind_of_batch_and_matches_per_batch_calls(flags):
+    """upload.rank_batches (through Diffusion.test_atk) on every kind of batch a loader can hand over, with the same pixels in each:
+    (a) pinned fp32, (b) pageable contiguous fp32 (the single-thread staging memcpy), (c) pageable float64 and (d) a pageable
+    non-contiguous fp32 view (both through Tensor.copy_ into the pinned buffer), (e) batches already on the device, (f) a loader of
+    exactly one batch.  Without a flag (a)-(d) and (f) go straight into the library's input buffer, with brightness=0.1 through the two
+    staging buffers and perturb; (e) is always handed to perturb as it is.  Every one must give exactly the probabilities of per-batch
+    predict_batch(perturb(x.cuda())) calls on a twin runner with the same seed -- the same kernels in the same order on the same bytes --
+    and count only the host bytes that crossed PCIe."""
+    make, batches, B, img, C = loader_loop_case()
+    twin = make(**flags)
+    assert list(twin._rank_batches([], 0, B, B)) == [] and twin.bytes_uploaded == 0          # an empty loader: nothing, before any engine
+    twin.load_noise_estimators(max_batch=B)
+    twin._seed_noise(0)
+    want = torch.cat([twin.predict_batch(twin.perturb(x.cuda()))["prob"] for x, _ in batches])
+    assert not torch.equal(want[:B], want[B:2 * B])
+    turned = [x.transpose(2, 3).contiguous().transpose(2, 3) for x, _ in batches]            # the same pixels, rows and columns swapped in memory
+    assert all(not v.is_contiguous() and torch.equal(v, x) for v, (x, _) in zip(turned, batches))
+    loaders = {"pinned": [(x.pin_memory(), t) for x, t in batches],
+               "pageable": [(x.clone(), t) for x, t in batches],
+               "float64": [(x.double(), t) for x, t in batches],
+               "noncontiguous": [(v, t) for v, (_, t) in zip(turned, batches)],
+               "device": [(x.cuda(), t.cuda()) for x, t in batches],
+               "one_batch": [(batches[0][0].clone(), batches[0][1])]}
+    assert loaders["pinned"][0][0].is_pinned() and not loaders["pageable"][0][0].is_pinned() and loaders["float64"][0][0].dtype == torch.float64
+    for kind, loader in loaders.items():
+        n = len(loader)
+        loop = make(**flags)
+        loop.test_atk(test_loader=loader)
+        torch.cuda.synchronize()
+        assert torch.equal(loop.last_probs, want[:n * B]), (kind, flags)
+        assert loop.bytes_uploaded == (0 if kind == "device" else n * B * 3 * img * img * 4), (kind, flags)
+        if not flags and kind != "device":                                                   # the direct path, and its flag counted every batch
+            assert loop.engine._batch_calls == n and int(loop.engine._input_flag[0]) == n, kind
+        else:
+            assert getattr(loop.engine, "_input_flag", None) is None, kind
 
 
 def test_module_and_p_sample_loop_dropin():

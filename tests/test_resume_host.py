@@ -169,3 +169,83 @@ def test_fit_with_default_arguments_writes_no_snapshot(tmp_path, capsys):
     tr._fit(["T"], "VALID", 2, str(tmp_path / "best.pth"), "Stub", snapshot_path=str(tmp_path / "best.ckpt"))
     assert sorted(os.listdir(str(tmp_path))) == ["best.pth"]
     capsys.readouterr()
+
+
+# ---- 5. the run protocol: snapshot.load_run / save_run, and the loop that calls them ---------------------------------------------------------
+@pytest.fixture
+def rng_recorders(monkeypatch):
+    """snapshot.rng_state / set_rng_state touch the GPU generator: recorders in their place"""
+    from nested_diffusion_amd import snapshot
+    calls = []
+    monkeypatch.setattr(snapshot, "rng_state", lambda device, loader, engine=None: (calls.append(("get", device, loader, engine)), {"tag": 7})[1])
+    monkeypatch.setattr(snapshot, "set_rng_state", lambda state, device, loader, engine=None: calls.append(("set", state, device, loader, engine)))
+    return calls
+
+
+class StateStub:
+    def __init__(self):
+        self.loaded = []
+
+    def training_state(self):
+        return {"meta": {"format": 1}, "p": {"w": torch.arange(4.0)}, "t": 3}
+
+    def load_training_state(self, state):
+        self.loaded.append(state)
+
+
+def test_load_run_and_save_run_round_trip_on_a_stub_trainer(tmp_path, rng_recorders):
+    from nested_diffusion_amd import snapshot
+    path, tr = str(tmp_path / "run" / "ckpt.pth"), StateStub()
+    snapshot.save_run(path, tr, {"next_epoch": 2, "step": 6}, "dev", "LOADER", "ENGINE")
+    assert rng_recorders == [("get", "dev", "LOADER", "ENGINE")]
+    assert sorted(torch.load(path)) == ["loop", "rng", "trainer"] and os.listdir(os.path.dirname(path)) == ["ckpt.pth"]
+    snap = snapshot.load_run(path, tr)
+    assert sorted(snap) == ["loop", "rng", "trainer"] and snap["loop"] == {"next_epoch": 2, "step": 6} and snap["rng"] == {"tag": 7}
+    assert len(tr.loaded) == 1 and tr.loaded[0] is snap["trainer"]
+    got, want = tr.loaded[0], tr.training_state()
+    assert sorted(got) == sorted(want) and got["meta"] == want["meta"] and got["t"] == 3 and torch.equal(got["p"]["w"], want["p"]["w"])
+    assert len(rng_recorders) == 1                                                 # load_run leaves the generators to its caller
+    # a missing file is refused before the trainer is touched; a file without 'loop' is read's ValueError
+    fresh, missing = StateStub(), str(tmp_path / "run" / "none.pth")
+    with pytest.raises(FileNotFoundError) as e:
+        snapshot.load_run(missing, fresh)
+    assert missing in str(e.value) and fresh.loaded == []
+    torch.save({"trainer": want, "rng": {"tag": 7}}, missing)
+    with pytest.raises(ValueError, match="not a training snapshot: it has no 'loop' entry"):
+        snapshot.load_run(missing, fresh)
+    assert fresh.loaded == []
+
+
+def test_fit_resumed_from_the_epoch_2_snapshot_ends_as_the_straight_run(tmp_path, capsys, rng_recorders):
+    import shutil
+    accs, ckpt, aside = [0.5, 0.5, 0.75, 0.6], str(tmp_path / "best.ckpt"), str(tmp_path / "after_epoch_1.ckpt")
+
+    def stub(copy_at=None):
+        tr = make_stub(accs)
+        tr.training_state = lambda: {"epoch": tr.epoch}
+        tr.load_training_state = lambda state: setattr(tr, "epoch", int(state["epoch"]))
+        evaluate = tr.evaluate
+
+        def evaluate_and_copy(loader):
+            if tr.epoch == copy_at:                                                # the third epoch: the file holds the state after the second
+                shutil.copy(ckpt, aside)
+            return evaluate(loader)
+
+        tr.evaluate = evaluate_and_copy
+        return tr
+
+    straight = stub(copy_at=2)._fit("TRAIN", "VALID", 4, str(tmp_path / "best.pth"), "Stub", snapshot_path=ckpt, snapshot_epochs=2)
+    lines_a = capsys.readouterr().out.splitlines()
+    assert [c[0] for c in rng_recorders] == ["get", "get"] and all(c[1:] == ("cpu", "TRAIN", None) for c in rng_recorders)
+    half = torch.load(aside)
+    assert sorted(half) == ["loop", "rng", "trainer"] and sorted(half["loop"]) == ["best_acc", "best_train_acc", "next_epoch", "saved_epochs"]
+    assert half["loop"]["next_epoch"] == 2 and half["trainer"] == {"epoch": 2} and torch.load(ckpt)["loop"]["next_epoch"] == 4
+    del rng_recorders[:]
+    tr = stub()
+    resumed = tr._fit("TRAIN", "VALID", 4, str(tmp_path / "best.pth"), "Stub", snapshot_path=aside, snapshot_epochs=2, resume=True)
+    lines_b = capsys.readouterr().out.splitlines()
+    assert resumed == straight and resumed["saved_epochs"] == [0, 2]
+    assert rng_recorders[0] == ("set", {"tag": 7}, "cpu", "TRAIN", None) and [c[0] for c in rng_recorders[1:]] == ["get"]
+    assert tr.calls == [("train", "TRAIN"), ("valid", "VALID")] * 2                # epochs 2 and 3 only
+    assert lines_b[0] == f"Resumed from {aside} at epoch 2"
+    assert lines_b[1:] == lines_a[4:] and len(lines_a) == 9 and lines_b[1].startswith("Epoch 2 Train") and lines_b[3].startswith("Epoch 3 Train")

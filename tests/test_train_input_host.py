@@ -248,3 +248,38 @@ def test_make_loaders_without_a_cache_is_the_dataloader_and_names_its_cache_file
     assert tm.cache_file("d", "training", train.dataset) == os.path.join("d", "training_grayscaled_224x224.npz")
     with pytest.raises(ValueError, match="cache"):
         tm.make_loaders(str(tmp_path), "ChestXRay", "grayscaled", 4, 3, cache="host")
+
+
+def test_split_loader_builds_both_training_paths_loaders_from_their_arguments(tmp_path):
+    """data.split_loader is the one place that turns a split into a loader: through train_mapping.make_loaders' arguments a shuffled
+    DataLoader on the seeded generator, nothing dropped; through the noise-estimator loop's (train_diffusion.default_loader) num_workers
+    from the config and drop_last on validation.  Each refusal names its own flag."""
+    import argparse
+    from nested_diffusion_amd import _trainer, train_diffusion as td, train_mapping as tm, train_transformer as tt
+    assert tm.make_loaders is tt.make_loaders is _trainer.make_loaders and tm.snapshot_settings is _trainer.snapshot_settings
+    ns = argparse.Namespace
+    tree(str(tmp_path / "training"))                                                # 6 images
+    tree(str(tmp_path / "validation"), n_per_class=4)
+    os.remove(str(tmp_path / "validation" / "b" / "3.png"))                          # 7 images
+    train, valid = tm.make_loaders(str(tmp_path), "ChestXRay", "grayscaled", 4, 3, image_size=(8, 8))
+    assert isinstance(train, torch.utils.data.DataLoader) and isinstance(train.sampler, torch.utils.data.RandomSampler)
+    assert isinstance(train.generator, torch.Generator) and train.generator.initial_seed() == 3 and train.num_workers == 0
+    assert not train.drop_last and not valid.drop_last and isinstance(valid.sampler, torch.utils.data.SequentialSampler)
+    assert valid.generator is None and len(train) == 2 and len(valid) == 1 and valid.batch_size == tm.VALID_BATCH
+    ref = torch.utils.data.DataLoader(train.dataset, batch_size=4, shuffle=True, generator=torch.Generator().manual_seed(3))
+    assert all(torch.equal(a[1], b[1]) and torch.equal(a[0], b[0]) for a, b in zip(train, ref))
+    # the noise-estimator loop's arguments
+    cfg = ns(data=ns(dataroot=str(tmp_path), dataset="ChestXRay", num_workers=2), model=ns(data_dim=3 * 8 * 8))
+    args = ns(preprocess="grayscaled")
+    train = td.default_loader(args, cfg, "cuda", "training", 4, shuffle=True)
+    valid = td.default_loader(args, cfg, "cuda", "validation", 3, shuffle=False, drop_last=True)
+    assert isinstance(train, torch.utils.data.DataLoader) and train.num_workers == valid.num_workers == 2 and train.generator is None
+    assert isinstance(train.sampler, torch.utils.data.RandomSampler) and train.dataset.size == (8, 8) and not train.drop_last
+    assert valid.drop_last and len(valid.dataset) == 7 and len(valid) == 2 and isinstance(valid.sampler, torch.utils.data.SequentialSampler)
+    # both refusals, word for word
+    with pytest.raises(ValueError) as e:
+        tm.make_loaders(str(tmp_path), "ChestXRay", "grayscaled", 4, 3, cache="host")
+    assert str(e.value) == "cache must be one of ('none', 'device') (cache='host')"
+    with pytest.raises(ValueError) as e:
+        td.default_loader(ns(preprocess="grayscaled", train_cache="host"), cfg, "cuda", "training", 4, shuffle=True)
+    assert str(e.value) == "train_cache must be one of ('none', 'device') (train_cache='host')"
