@@ -1,6 +1,6 @@
 // nd_attention_h.hip -- the fp16-operand attention core of the ViT blocks (the fp16 mode; head dim 64), behind nd_launch_attention_h.
 // gfx950 only.  A unit of its own: the fp32 kernels of nd_attention.hip are built with -mllvm -amdgpu-mfma-vgpr-form, this one is not.
-// Entry points and the MFMA operand maps shared by the three forms: nd_attention.hip.
+// Entry points and the MFMA operand maps it shares with the RING kernel: nd_attention.hip.
 #include "nd_math.hpp"
 #include "nd_device.hpp"
 #include "nd_vit.hpp"

@@ -68,7 +68,7 @@ __device__ __forceinline__ void nd_b9_store4(bf16x8* img, int nkb, int r, int k,
 }
 
 // ---- "qkv images": the attention operands of one (image, head), written by the qkv GEMM's epilogue (nd_gemm_b9.hip, ATT form) and
-// read by k_attention_b9 (nd_attention.hip).  One record per (image b, head h) at 16-byte-unit offset (b*heads + h) * units():
+// read by k_attention_b9 (nd_attention_b9.hip).  One record per (image b, head h) at 16-byte-unit offset (b*heads + h) * units():
 //   Q   nfq x 2 blocks   block (f, c) = (16 query rows of fragment f) x (d = 32c .. 32c+31): plain frag32b3 blocks, k = d
 //   K   nfq x 2 blocks   the same for the keys
 //   V^T 4 x nkb blocks   block (df, kb) = (d = 16 df .. +15) x (32 keys of block kb), k = key, the keys of a block PERMUTED: position
@@ -118,7 +118,7 @@ __device__ __forceinline__ void b9_stage_pieces(const bf16x8* const (&src)[NP], 
 // lane l of acc[i][j] holds D[n = 4*(l>>4) + r][m = l&15], i.e. 4 consecutive output columns n of activation row m.
 // SWAP: the operand roles of the MFMA exchanged (A = x fragment, B = w fragment): lane l of acc[i][j] then holds D[m = 4*(l>>4) + r][n = l&15],
 // i.e. 4 consecutive ACTIVATION rows m of output column n -- the form whose frag32b3 store is the TRANSPOSED image (k = m contiguous):
-// the V^T operand of the attention's P V contraction (nd_attention.hip, k_attention_b9).  Same products, same order of terms.
+// the V^T operand of the attention's P V contraction (nd_attention_b9.hip, k_attention_b9).  Same products, same order of terms.
 template <int FA, int FB, int WN, int WM, int NS, unsigned NTMASK = 0u, bool SWAP = false>
 __device__ __forceinline__ void b9_mainloop_impl(f32x4 (&acc)[FA][FB], const bf16x8* (&src)[(((WN * FA + WM * FB) * 3) + WN * WM - 1) / (WN * WM)],
                                                  bf16x8* lds, int nk, int wave, int wn, int wm, int lane) {
@@ -206,4 +206,30 @@ __device__ __forceinline__ void b9_mainloop(f32x4 (&acc)[FA][FB], const bf16x8* 
             default: b9_mainloop_impl<FA, FB, WN, WM, NS, 63u>(acc, src, lds, nk, wave, wn, wm, lane); break;
         }
     }
+}
+
+// src[] of b9_mainloop for one tile, at K-step c0 of nkb: the tile's w fragments are wf0 .. wf0 + WN*FA - 1 of the nfr of image ws, its x
+// fragments xf0 .. xf0 + WM*FB - 1 of the mfr of image xs; fragment indices past the matrix edge are clamped (their products are never stored)
+template <int FA, int FB, int WN, int WM>
+__device__ __forceinline__ void b9_tile_sources(const bf16x8* (&src)[(((WN * FA + WM * FB) * 3) + WN * WM - 1) / (WN * WM)], const bf16x8* ws,
+                                                const bf16x8* xs, int wf0, int xf0, int nfr, int mfr, int nkb, int c0, int wave, int lane) {
+    constexpr int NW = WN * WM, NPC = (WN * FA + WM * FB) * 3, NP = (NPC + NW - 1) / NW;
+#pragma unroll
+    for (int u = 0; u < NP; ++u) {
+        const int e = min(wave * NP + u, NPC - 1), f = e / 3, pl = e % 3;
+        const bf16x8* base = f < WN * FA ? ws + ((size_t)min(wf0 + f, nfr - 1) * nkb + c0) * B9_BLOCK_UNITS
+                                         : xs + ((size_t)min(xf0 + f - WN * FA, mfr - 1) * nkb + c0) * B9_BLOCK_UNITS;
+        src[u] = base + pl * 64 + lane;
+    }
+}
+
+// raw accumulators of k-slab number `slab_index` of a launch of NW-wave workgroups: [slab][wave][fragment][lane], one coalesced 1 KiB store
+// per fragment
+template <int NW, int FA, int FB>
+__device__ __forceinline__ void b9_store_partial(f32x4* part, size_t slab_index, int wave, int lane, const f32x4 (&acc)[FA][FB]) {
+    f32x4* pt = part + (slab_index * NW + wave) * (FA * FB) * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < FA; ++i)
+#pragma unroll
+        for (int j = 0; j < FB; ++j) *(__attribute__((address_space(1))) f32x4*)(pt + (i * FB + j) * 64) = acc[i][j];
 }

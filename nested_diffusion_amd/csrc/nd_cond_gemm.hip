@@ -3,26 +3,18 @@
 #include "nd_cond_gemm.hpp"
 #include "nd_frag.hpp"
 #include "nd_b9.hpp"
+#include "nd_tile.hpp"
 
 // which 128 x 128 tile a workgroup owns, and (slab >= 0) which k-slab of it
 struct CondGemmTile { int member, tm, tn, slab, rem_index; };
 
 __device__ __forceinline__ CondGemmTile cg_decode(int bid, int n_full, int split, int TM, int TN) {
+    const NdTile t = nd_tile_decode(bid, n_full, split);
     CondGemmTile tl;
-    tl.slab = -1; tl.rem_index = 0;
-    if (bid < n_full) {
-        // blocks b and b + 8 share an XCD (round-robin dispatch): XCD x takes the contiguous run of tiles [x*q, (x+1)*q)
-        const int q = n_full / 8, r = n_full % 8, xcd = bid % 8, loc = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    } else {
-        const int j = bid - n_full;
-        tl.rem_index = j / split;
-        tl.slab = j % split;
-        bid = n_full + tl.rem_index;
-    }
+    tl.slab = t.slab; tl.rem_index = t.rem_index;
     const int per = TM * TN;
-    tl.member = bid / per;
-    const int r2 = bid - tl.member * per;
+    tl.member = t.tile / per;
+    const int r2 = t.tile - tl.member * per;
     tl.tn = r2 / TM;
     tl.tm = r2 - tl.tn * TM;
     return tl;
@@ -78,6 +70,8 @@ __device__ __forceinline__ void cg_epilogue_g(f32x4 (&acc)[FI][FJ], const Skinny
                         for (int r = 0; r < 4; ++r) if (n0 + r >= N) v[r] = 0.f;
                         *(__attribute__((address_space(1))) f32x4*)(d.out + ((size_t)mf * nfr + nf) * 256 + lane * 4) = v;
                     } else if (m < M) {
+                        // nd_store_row4 (nd_tile.hpp) with the 16-byte store named global: d.out comes out of a descriptor table, where
+                        // the compiler cannot infer the address space
                         float* p = d.out + (size_t)m * N + n0;
                         if (n0 + 3 < N && (N & 3) == 0) *(__attribute__((address_space(1))) f32x4*)p = acc[i][j];
                         else {
@@ -141,9 +135,7 @@ __global__ __launch_bounds__(256) void k_cond_gemm(SkinnyDesc d0, const SkinnyDe
     const SkinnyDesc d = table ? table[tl.member] : d0;
     const int K = __builtin_amdgcn_readfirstlane(d.K), N = __builtin_amdgcn_readfirstlane(d.N);     // uniform: keeps the loop scalar
     const int nch = K >> 4, nfr = (N + 15) >> 4, mfr = (M + 15) >> 4;
-    const int c0 = tl.slab < 0 ? 0 : (int)((long)tl.slab * nch / split);
-    const int c1 = tl.slab < 0 ? nch : (int)((long)(tl.slab + 1) * nch / split);
-    const int nk = c1 - c0;
+    const int c0 = nd_slab_begin(tl.slab, nch, split), nk = nd_slab_end(tl.slab, nch, split) - c0;
 
     // staging: wave w brings fragments 4w .. 4w+3 of a slot (waves 0,1: the tile's 8 W fragments; waves 2,3: its 8 x fragments);
     // fragment indices past the matrix edge are clamped (their products are never stored)
@@ -301,18 +293,11 @@ __global__ __launch_bounds__(512) void k_cond_gemm_b9(SkinnyDesc d0, const Skinn
     const SkinnyDesc d = table ? table[tl.member] : d0;
     const int K = __builtin_amdgcn_readfirstlane(d.K), N = __builtin_amdgcn_readfirstlane(d.N);
     const int nkb = K >> 5, nfr = (N + 15) >> 4, mfr = (M + 15) >> 4;
-    const int c0 = tl.slab < 0 ? 0 : (int)((long)tl.slab * nkb / split);
-    const int c1 = tl.slab < 0 ? nkb : (int)((long)(tl.slab + 1) * nkb / split);
+    const int c0 = nd_slab_begin(tl.slab, nkb, split), c1 = nd_slab_end(tl.slab, nkb, split);
     const bf16x8* wbase = reinterpret_cast<const bf16x8*>(cg_uniform_ptr(d.w));
     const bf16x8* xbase = reinterpret_cast<const bf16x8*>(cg_uniform_ptr(d.x));
     const bf16x8* src[NP];
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-        const int e = min(wave * NP + u, NPC - 1), f = e / 3, pl = e % 3;
-        const bf16x8* base = f < CG_F ? wbase + ((size_t)min(tl.tn * CG_F + f, nfr - 1) * nkb + c0) * B9_BLOCK_UNITS
-                                      : xbase + ((size_t)min(tl.tm * CG_F + f - CG_F, mfr - 1) * nkb + c0) * B9_BLOCK_UNITS;
-        src[u] = base + pl * 64 + lane;
-    }
+    b9_tile_sources<CG9_FA, CG9_FB, CG9_WN, CG9_WM>(src, wbase, xbase, tl.tn * CG_F, tl.tm * CG_F, nfr, mfr, nkb, c0, wave, lane);
     f32x4 acc[CG9_FA][CG9_FB];
 #pragma unroll
     for (int i = 0; i < CG9_FA; ++i)
@@ -320,11 +305,7 @@ __global__ __launch_bounds__(512) void k_cond_gemm_b9(SkinnyDesc d0, const Skinn
         for (int j = 0; j < CG9_FB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     b9_mainloop<CG9_FA, CG9_FB, CG9_WN, CG9_WM, CG9_NS, CG9_NTW>(acc, src, lds9, c1 - c0, wave, wn, wm, lane);
     if (tl.slab >= 0) {     // [remainder tile][slab][wave][fragment][lane]: 8 waves x 8 fragments x 1 KiB = one 128 x 128 fp32 tile
-        float* pt = ws + ((size_t)tl.rem_index * split + tl.slab) * (CG_T * CG_T) + (size_t)wave * (CG9_FA * CG9_FB) * 256 + lane * 4;
-#pragma unroll
-        for (int i = 0; i < CG9_FA; ++i)
-#pragma unroll
-            for (int j = 0; j < CG9_FB; ++j) *(__attribute__((address_space(1))) f32x4*)(pt + (i * CG9_FB + j) * 256) = acc[i][j];
+        b9_store_partial<NW>(reinterpret_cast<f32x4*>(ws), (size_t)tl.rem_index * split + tl.slab, wave, lane, acc);
         return;
     }
     cg_epilogue_g<MODE, CG9_FA, CG9_FB>(acc, d, M, t, tl.tn * CG_F + wn * CG9_FA, tl.tm * CG_F + wm * CG9_FB, tl.tn * 2 + wn, lane, 2 * TN);

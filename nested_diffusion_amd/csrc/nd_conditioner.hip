@@ -1,6 +1,6 @@
 // nd_conditioner.hip -- the mapping network as ONE C-level call (gfx950 only): host-side sequencing of the ViT and
 // mapping-MLP kernels (ViT: nd_patchify.hip, nd_layernorm.hip, nd_gemm_nt.hip / nd_gemm_f32.hip / nd_gemm_b9.hip, nd_attention.hip /
-// nd_attention_h.hip; mapping MLPs: nd_linear.hip; the conditions' softmax: nd_report.hip).
+// nd_attention_b9.hip / nd_attention_h.hip; mapping MLPs: nd_linear.hip; the conditions' softmax: nd_report.hip).
 //
 // Reference (file:line relative to the reference checkout):
 //   diffusion/classification_train_separately.py:249-275   cond_pred_model = {'vit', 'mlps'} (whole-module pickles)

@@ -15,6 +15,7 @@
 // Epilogue (kernel and fixup alike): bias, activation, residual, then fp32 row-major store and / or a frag32b3 store of the result
 // for the GEMM that consumes it (fc1 -> fc2), so that no separate pass ever splits an activation.
 #include "nd_b9.hpp"
+#include "nd_tile.hpp"
 #include <cstdlib>
 #include "nd_host.hpp"
 #include "nd_device.hpp"
@@ -59,31 +60,12 @@ __device__ __forceinline__ void b9_epilogue_att_v(const B9Epilogue& e, f32x4 a, 
     nd_b9_store4_at(blk, (d & 15) + 16 * ((w & 15) >> 2), w >> 4, a[0] + bn, a[1] + bn, a[2] + bn, a[3] + bn);
 }
 
-// bias, activation, residual of the lane's 4 consecutive output columns n0 .. n0+3 of row m (m < M, n0 < N)
-__device__ __forceinline__ void b9_epilogue_values(const B9Epilogue& e, f32x4 a, int m, int n0, int N, float (&v)[4]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int nn = min(n0 + r, N - 1);
-        float t = a[r] + (e.bias ? e.bias[nn] : 0.f);
-        t = nd_act(t, e.act);
-        if (e.res && n0 + r < N) t += e.res[(size_t)m * N + n0 + r];
-        v[r] = t;
-    }
-}
-
 // lane's 4 consecutive output columns n0 .. n0+3 of row m
 __device__ __forceinline__ void b9_epilogue(const B9Epilogue& e, f32x4 a, int m, int n0, int M, int N) {
     if (m >= M || n0 >= N) return;
     float v[4];
-    b9_epilogue_values(e, a, m, n0, N, v);
-    if (e.out) {
-        float* p = e.out + (size_t)m * N + n0;
-        if (n0 + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (n0 + r < N) p[r] = v[r];
-        }
-    }
+    nd_gemm_values4(a, e.bias, e.res, e.act, m, n0, N, v);
+    if (e.out) nd_store_row4(e.out, m, n0, N, v);
     if (e.out_split) nd_b9_store4(e.out_split, N >> 5, m, n0, v[0], v[1], v[2], v[3]);     // N % 32 == 0 (checked on the host)
 }
 
@@ -110,13 +92,7 @@ __global__ __launch_bounds__(64 * WN * WM) void k_gemm_b9(const bf16x8* __restri
             const int nkb = K >> 5, nfr = (N + 15) >> 4, mfr = (M + 15) >> 4;
             const int mf0 = tm * WM * FB + half * WM * HB;              // first x fragment of this half tile
             const bf16x8* src[HP];
-#pragma unroll
-            for (int u = 0; u < HP; ++u) {
-                const int e = min(wave * HP + u, HPC - 1), f = e / 3, pl = e % 3;
-                const bf16x8* base = f < WN * FA ? ws + (size_t)min(tn * WN * FA + f, nfr - 1) * nkb * B9_BLOCK_UNITS
-                                                 : xs + (size_t)min(mf0 + f - WN * FA, mfr - 1) * nkb * B9_BLOCK_UNITS;
-                src[u] = base + pl * 64 + lane;
-            }
+            b9_tile_sources<FA, HB, WN, WM>(src, ws, xs, tn * WN * FA, mf0, nfr, mfr, nkb, 0, wave, lane);
             f32x4 acc[FA][HB];
 #pragma unroll
             for (int i = 0; i < FA; ++i)
@@ -149,28 +125,12 @@ __global__ __launch_bounds__(64 * WN * WM) void k_gemm_b9(const bf16x8* __restri
             return;
         }
     }
-    int bid = blockIdx.x, slab = -1, rem_index = 0;
-    if (bid < n_full) {
-        // blocks b and b + 8 share an XCD (round-robin dispatch): XCD x takes a contiguous run of tiles, n fastest, so the workgroups
-        // that share an L2 share an x panel
-        const int q = n_full / 8, r = n_full % 8, xcd = bid % 8, loc = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    } else {
-        const int j = bid - n_full;
-        rem_index = j / split; slab = j % split; bid = n_full + rem_index;
-    }
-    const int tm = bid / TN, tn = bid - tm * TN;
+    const NdTile tl = nd_tile_decode(blockIdx.x, n_full, split);     // tiles n fastest: the workgroups that share an L2 share an x panel
+    const int tm = tl.tile / TN, tn = tl.tile - tm * TN;
     const int nkb = K >> 5, nfr = (N + 15) >> 4, mfr = (M + 15) >> 4;
-    const int c0 = slab < 0 ? 0 : (int)((long)slab * nkb / split), c1 = slab < 0 ? nkb : (int)((long)(slab + 1) * nkb / split);
+    const int c0 = nd_slab_begin(tl.slab, nkb, split), c1 = nd_slab_end(tl.slab, nkb, split);
     const bf16x8* src[NP];
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-        const int e = min(wave * NP + u, NPC - 1), f = e / 3, pl = e % 3;
-        // fragment indices past the matrix edge are clamped (their products are never stored)
-        const bf16x8* base = f < WN * FA ? ws + ((size_t)min(tn * WN * FA + f, nfr - 1) * nkb + c0) * B9_BLOCK_UNITS
-                                         : xs + ((size_t)min(tm * WM * FB + f - WN * FA, mfr - 1) * nkb + c0) * B9_BLOCK_UNITS;
-        src[u] = base + pl * 64 + lane;
-    }
+    b9_tile_sources<FA, FB, WN, WM>(src, ws, xs, tn * WN * FA, tm * WM * FB, nfr, mfr, nkb, c0, wave, lane);
     f32x4 acc[FA][FB];
 #pragma unroll
     for (int i = 0; i < FA; ++i)
@@ -195,12 +155,8 @@ __global__ __launch_bounds__(64 * WN * WM) void k_gemm_b9(const bf16x8* __restri
         return;
     }
     b9_mainloop<FA, FB, WN, WM, NS>(acc, src, lds, c1 - c0, wave, wn, wm, lane);
-    if (slab >= 0) {     // raw accumulators of a k-slab: [remainder tile][slab][wave][fragment][lane], one coalesced 1 KiB store per fragment
-        f32x4* pt = part + (((size_t)rem_index * split + slab) * NW + wave) * (FA * FB) * 64 + lane;
-#pragma unroll
-        for (int i = 0; i < FA; ++i)
-#pragma unroll
-            for (int j = 0; j < FB; ++j) *(__attribute__((address_space(1))) f32x4*)(pt + (i * FB + j) * 64) = acc[i][j];
+    if (tl.slab >= 0) {
+        b9_store_partial<NW>(part, (size_t)tl.rem_index * split + tl.slab, wave, lane, acc);
         return;
     }
     // fp32 row-major output of an interior tile: through LDS, so that the global stores are whole 512-byte row segments.  In the MFMA
@@ -223,7 +179,7 @@ __global__ __launch_bounds__(64 * WN * WM) void k_gemm_b9(const bf16x8* __restri
             for (int j = 0; j < FB; ++j) {
                 const int ml = (wm * FB + j) * 16 + (lane & 15), nl = (wn * FA + i) * 16 + 4 * (lane >> 4);
                 float v[4];
-                b9_epilogue_values(ep, acc[i][j], tm * BMc + ml, tn * BNc + nl, N, v);
+                nd_gemm_values4(acc[i][j], ep.bias, ep.res, ep.act, tm * BMc + ml, tn * BNc + nl, N, v);
                 *reinterpret_cast<f32x4*>(stage + ml * SLD + nl) = f32x4{v[0], v[1], v[2], v[3]};
             }
         __syncthreads();

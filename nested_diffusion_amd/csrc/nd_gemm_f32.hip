@@ -12,7 +12,7 @@
 // every memory instruction issues in the shadow of running MFMAs.
 // LDS rows are 16 floats + 8 pad: a lane's float4 (k = 4*(l>>4)..+3) is one conflict-free ds_read_b128; MFMA jj takes element jj
 // of every lane (k order permuted identically on both operands).
-#include "nd_math.hpp"
+#include "nd_tile.hpp"
 #include "nd_vit.hpp"      // GB_K, GB_LD: shared with the plan of nd_gemm_nt.hip
 
 template <int BM, int BN>
@@ -33,16 +33,8 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, co
     // Workgroups [0, n_full) take one whole tile each; the remaining tiles are cut into `split` k-slabs, one workgroup per
     // slab, whose raw sums go to `part` and are finished by k_gemm_fixup (the tail of the launch is then `split` times finer).
     const int tiles_n = (N + BN - 1) / BN;
-    int bid = blockIdx.x, slab = -1;
-    if (bid < n_full) {
-        const int q = n_full / 8, r = n_full % 8, xcd = bid % 8, loc = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    } else {
-        const int j = bid - n_full;
-        bid = n_full + j / split;
-        slab = j % split;
-    }
-    const int tm = bid / tiles_n, tn = bid % tiles_n;
+    const NdTile tl = nd_tile_decode(blockIdx.x, n_full, split);
+    const int tm = tl.tile / tiles_n, tn = tl.tile % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
 
     f32x4 acc[FM][FN];
@@ -83,9 +75,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, co
                 _Pragma("unroll") for (int j = 0; j < FN; ++j)                                                            \
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[set][j][q], fa[set][i][q], acc[i][j], 0, 0, 0);   \
     }
-    const int nkt = K / GB_K;
-    const int ks0 = slab < 0 ? 0 : (int)((long)slab * nkt / split);
-    const int nk = slab < 0 ? nkt : (int)((long)(slab + 1) * nkt / split);
+    const int ks0 = nd_slab_begin(tl.slab, K / GB_K, split), nk = nd_slab_end(tl.slab, K / GB_K, split);
     const int lr = lane & 15, lk = 4 * (lane >> 4);
     constexpr int NMQ = FM * FN;                       // MFMAs per k-quad
     constexpr int NW = LA + LB, NR = FM + FN;          // LDS writes / global loads, and fragment reads, per step
@@ -136,13 +126,8 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, co
 #undef GB_READ
 #undef GB_MMA
     // D[n = 4*(l>>4)+r][m = l&15]: a lane owns 4 consecutive n of one row m
-    if (slab >= 0) {
-        float* pt = part + ((size_t)(bid - n_full) * split + slab) * (BM * BN);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-                *reinterpret_cast<f32x4*>(pt + (wr * WM + 16 * i + (lane & 15)) * BN + wc * WN + 16 * j + 4 * (lane >> 4)) = acc[i][j];
+    if (tl.slab >= 0) {
+        nd_gemm_store_partial(part + ((size_t)tl.rem_index * split + tl.slab) * (BM * BN), acc, wr * WM + (lane & 15), wc * WN + 4 * (lane >> 4));
         return;
     }
 #pragma unroll
@@ -151,23 +136,7 @@ __global__ __launch_bounds__(256) void k_gemm_nt(const float* __restrict__ x, co
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
             const int n = n0 + wc * WN + 16 * j + 4 * (lane >> 4);
-            if (m < M && n < N) {
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int nn = min(n + r, N - 1);
-                    float t = acc[i][j][r] + (bias ? bias[nn] : 0.f);
-                    t = nd_act(t, act);
-                    if (res && n + r < N) t += res[(size_t)m * N + n + r];
-                    v[r] = t;
-                }
-                float* p = out + (size_t)m * N + n;
-                if (n + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < N) p[r] = v[r];
-                }
-            }
+            if (m < M && n < N) nd_gemm_finish4(acc[i][j], bias, res, out, act, m, n, N);
         }
     }
 }

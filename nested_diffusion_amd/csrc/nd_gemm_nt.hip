@@ -1,7 +1,7 @@
 // nd_gemm_nt.hip -- the large-M GEMM of the ViT (nd_gemm_bias_act; timm 0.4.12 vit_base_patch16_224 semantics, call sites
 // classification_train_separately.py:337-340): entry point, tile plan, k-split fixup and the fp16-operand kernel k_gemm_h.  gfx950 only.
 // The fp32 kernel k_gemm_nt<128,64> is a unit of its own (nd_gemm_f32.hip: accumulators in VGPRs) behind nd_launch_gemm_nt_128x64.
-#include "nd_math.hpp"
+#include "nd_tile.hpp"
 #include "nd_device.hpp"
 #include "nd_host.hpp"
 #include "nd_vit.hpp"
@@ -28,16 +28,8 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ x, con
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int tiles_n = (N + BN - 1) / BN;
-    int bid = blockIdx.x, slab = -1;
-    if (bid < n_full) {
-        const int q = n_full / 8, r = n_full % 8, xcd = bid % 8, loc = bid / 8;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    } else {
-        const int j = bid - n_full;
-        bid = n_full + j / split;
-        slab = j % split;
-    }
-    const int tm = bid / tiles_n, tn = bid % tiles_n;
+    const NdTile tl = nd_tile_decode(blockIdx.x, n_full, split);
+    const int tm = tl.tile / tiles_n, tn = tl.tile % tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -69,9 +61,7 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ x, con
             *reinterpret_cast<f16x8*>(&sB[buf][row][kq]) = rb[i];                                         \
         }                                                                                                 \
     }
-    const int nkt = K / GH_K;
-    const int ks0 = slab < 0 ? 0 : (int)((long)slab * nkt / split);
-    const int nk = slab < 0 ? nkt : (int)((long)(slab + 1) * nkt / split);
+    const int ks0 = nd_slab_begin(tl.slab, K / GH_K, split), nk = nd_slab_end(tl.slab, K / GH_K, split);
     GH_GLOAD(ks0 * GH_K)
     GH_SWRITE(ks0 & 1)
     __syncthreads();
@@ -93,14 +83,8 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ x, con
     }
 #undef GH_GLOAD
 #undef GH_SWRITE
-    if (slab >= 0) {
-        float* pt = part + ((size_t)(bid - n_full) * split + slab) * (BM * BN);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j)
-                *reinterpret_cast<float4*>(pt + (wr * WM + 16 * i + (lane & 15)) * BN + wc * WN + 16 * j + 4 * (lane >> 4)) =
-                    make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+    if (tl.slab >= 0) {
+        nd_gemm_store_partial(part + ((size_t)tl.rem_index * split + tl.slab) * (BM * BN), acc, wr * WM + (lane & 15), wc * WN + 4 * (lane >> 4));
         return;
     }
 #pragma unroll
@@ -109,23 +93,7 @@ __global__ __launch_bounds__(256) void k_gemm_h(const float* __restrict__ x, con
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
             const int n = n0 + wc * WN + 16 * j + 4 * (lane >> 4);
-            if (m < M && n < N) {
-                float v[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int nn = min(n + r, N - 1);
-                    float t = acc[i][j][r] + (bias ? bias[nn] : 0.f);
-                    t = nd_act(t, act);
-                    if (res && n + r < N) t += res[(size_t)m * N + n + r];
-                    v[r] = t;
-                }
-                float* p = out + (size_t)m * N + n;
-                if (n + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-                else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (n + r < N) p[r] = v[r];
-                }
-            }
+            if (m < M && n < N) nd_gemm_finish4(acc[i][j], bias, res, out, act, m, n, N);
         }
     }
 }
@@ -148,21 +116,7 @@ __global__ __launch_bounds__(256) void k_gemm_fixup(const float* __restrict__ pa
         const float4 v = *reinterpret_cast<const float4*>(pt + (size_t)k * (BM * BN));
         s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w;
     }
-    float v[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int nn = min(n + r, N - 1);
-        float t = v[r] + (bias ? bias[nn] : 0.f);
-        t = nd_act(t, act);
-        if (res && n + r < N) t += res[(size_t)m * N + n + r];
-        v[r] = t;
-    }
-    float* p = out + (size_t)m * N + n;
-    if (n + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (n + r < N) p[r] = v[r];
-    }
+    nd_gemm_finish4(f32x4{s4.x, s4.y, s4.z, s4.w}, bias, res, out, act, m, n, N);
 }
 
 // Launch plan.  Measured (tools/bench_gemm2.py): the run time of a launch is ceil(tiles / 256) x (time of one tile), i.e. it

@@ -1,5 +1,5 @@
-// nd_vit.hpp -- what the ViT units share (nd_gemm_nt.hip, nd_gemm_f32.hip, nd_layernorm.hip, nd_attention.hip, nd_attention_h.hip,
-// nd_vit_grad.hip): the launchers one unit defines and another calls, the tile constants a launch plan and its kernel must agree on,
+// nd_vit.hpp -- what the ViT units share (nd_gemm_nt.hip, nd_gemm_f32.hip, nd_layernorm.hip, nd_attention.hip, nd_attention_b9.hip,
+// nd_attention_h.hip, nd_vit_grad.hip): the launchers one unit defines and another calls, the tile constants a launch plan and its kernel must agree on,
 // and the two template dispatches.  The defining units include it too, so each signature exists once.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@ hipError_t nd_launch_gemm_nt_128x64(const float* x, const float* w, const float*
 // ---- attention core, d = 64: one launcher per form, each dispatching on NF = ceil(N / 16) key fragments ----
 #define AT_MAXF 16  // up to 256 keys
 hipError_t nd_launch_attention_ring(const float* qkv, float* out, int B, int N, int heads, int split_out, hipStream_t st);   // nd_attention.hip
-hipError_t nd_launch_attention_b9(const void* att, float* out, int B, int N, int heads, int split_out, hipStream_t st);      // nd_attention.hip
+hipError_t nd_launch_attention_b9(const void* att, float* out, int B, int N, int heads, int split_out, hipStream_t st);      // nd_attention_b9.hip
 hipError_t nd_launch_attention_h(const float* qkv, float* out, int B, int N, int heads, hipStream_t st);                     // nd_attention_h.hip
 
 // CALL(NF) for nf = 1 .. AT_MAXF as a compile-time constant; no case for any other nf

@@ -1,6 +1,6 @@
-"""The forward pieces of the ViT.  Binds csrc/nd_layernorm.hip, csrc/nd_attention.hip, csrc/nd_patchify.hip and the qkv-image entry
-points of csrc/nd_gemm_b9.hip (include/nested_diffusion.h: "standalone operators").  Each operator comes as a pair: the fp32 result, or
-(`*_split`) the same result written as the frag32b3 image the gemm_split after it reads."""
+"""The forward pieces of the ViT.  Binds csrc/nd_layernorm.hip, csrc/nd_attention.hip (with csrc/nd_attention_b9.hip), csrc/nd_patchify.hip
+and the qkv-image entry points of csrc/nd_gemm_b9.hip (include/nested_diffusion.h: "standalone operators").  Each operator comes as a
+pair: the fp32 result, or (`*_split`) the same result written as the frag32b3 image the gemm_split after it reads."""
 from __future__ import annotations
 
 from typing import Optional
