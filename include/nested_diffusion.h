@@ -626,6 +626,42 @@ int nd_cw_update(float *delta_dev, float *m_dev, float *v_dev, const float *dx_d
                  const float *t_dev, float *best_dev, const int32_t *flags_dev, int B, size_t per_image, float stepsize, float bc1,
                  float bc2, float b_half, void *stream);
 
+/* ---- AutoAttack's APGD, L2 (autopgd_base.py attack_single_run with norm = 'L2'; the listing: nested_diffusion_amd/autoattack.py), and the
+ * accumulation of an expectation over transformation (nested_diffusion_amd/eot.py); csrc/nd_apgd_l2.hip.  B images of per_image fp32
+ * elements (per_image % 4 == 0, 1 <= B <= 65535, images 16-byte aligned), checked before any HIP call, as is a NULL required pointer
+ * (ND_ERR_ARG).  Every elementwise operation is one rounded fp32 op in the listed order (contraction off).  No entry point allocates,
+ * copies synchronously or synchronises.  n(v)[b] = sqrtf(sum v^2) over image b is the row reduction of the L2 attacks above: grid
+ * (nd_l2_parts(per_image), B), per-workgroup partials in the workspace, a finishing pass with the same tree, no floating-point atomics:
+ * a norm has the same bits on every run and at every batch size.  ws: 2 * ND_L2_MAX_PARTS * B floats.
+ *   nd_apgd_l2_random_start  autoattack's L2 start: out = clip(x0 + eps * (t / (tn + 1e-12)), lo, hi), t per_image standard normals and
+ *                            tn = n(t), written to tnorm [B].  Normal 4q + e of row b comes from Philox4x32-10 with key = (seed low
+ *                            word, seed high word) and counter = (index[b] (low word), q, restart, ND_APGD_L2_START_TAG), the four
+ *                            words mapped by the Box-Muller of nd_rng exactly as in nd_l2_random_start.  Exactly per_image normals are
+ *                            drawn (no n + 2 extras: that is foolbox's ball).  index: int64 [B], the GLOBAL image index of each row, so
+ *                            a row of a compacted restart subset draws what it draws in the full batch.
+ *   nd_apgd_l2_step          the L2 momentum step of one iteration, in place.  Per row b, with xa the row's x_adv on entry, s = step[b]
+ *                            and g the row's gradient -- grad_best where flags[b] & ND_APGD_RESTORE, else grad; flags NULL: none (the
+ *                            first step, a = 1, with x_adv_old == x_adv; the two may be one buffer):
+ *                                g2 = xa - x_adv_old;  x_adv_old = xa
+ *                                gn = n(g);            u  = xa + s * (g / (gn + 1e-12))
+ *                                d1 = u - x;  n1 = n(d1);  z = clip(x + (d1 / (n1 + 1e-12)) * min(eps, n1), 0, 1)
+ *                                v  = (xa + (z - xa) * a) + g2 * (1 - a)
+ *                                d2 = v - x;  n2 = n(d2);  x_adv = clip(x + (d2 / (n2 + 1e-12)) * min(eps, n2), 0, 1)
+ *                            norms [3, B] receives gn, n1 and n2: exactly the values the elementwise passes used.  Later passes
+ *                            recompute the earlier elementwise values instead of storing them (the same bits).  A row whose gn is NaN
+ *                            or infinite takes no gradient step (u = xa), the convention of nd_l2_step.  Call order per iteration:
+ *                            nd_apgd_control, nd_apgd_update(..., do_step = 0) for the flags' copies and the restore (it writes x_best
+ *                            into a restored row's x_adv), then this.
+ *   nd_eot_add               acc = acc + g; with divisor > 0, acc = (acc + g) / (float)divisor: one add and one true division, not a
+ *                            reciprocal multiply.  n elements, n % 4 == 0, both 16-byte aligned. */
+#define ND_APGD_L2_START_TAG 0x41504C32u
+int nd_apgd_l2_random_start(const float *x0_dev, const int64_t *index_dev, float *out_dev, float *tnorm_dev, float *ws_dev, int B,
+                            size_t per_image, uint64_t seed, uint32_t restart, float eps, float lo, float hi, void *stream);
+int nd_apgd_l2_step(const float *x_dev, float *x_adv_dev, float *x_adv_old_dev, const float *grad_dev, const float *grad_best_dev,
+                    const int32_t *flags_dev, const float *step_dev, float *norms_dev, float *ws_dev, int B, size_t per_image, float eps,
+                    float a, void *stream);
+int nd_eot_add(float *acc_dev, const float *g_dev, size_t n, int divisor, void *stream);
+
 /* ---- the gradient through the mapping MLPs (csrc/nd_mlp_grad.hip; the chain: mapping.py GuidingConditioner.input_grad).  The ensemble
  * is conditioned on the mapping networks (patch_embed -> blocks[0..k] -> mlps[k] -> softmax), not on the full ViT's head: these two entry
  * points, with the ViT block gradients above, give the gradient of the conditioners' own loss with respect to the image.  Neither

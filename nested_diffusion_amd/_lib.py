@@ -196,6 +196,9 @@ SIGNATURES = {
     "nd_margin_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "nd_l2_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _vp]),
     "nd_l2_random_start": (_i, [_vp, _vp, _vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_apgd_l2_random_start": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _sz, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_apgd_l2_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _vp]),
+    "nd_eot_add": (_i, [_vp, _vp, _sz, _i, _vp]),
     "nd_cw_attack_space": (_i, [_vp, _vp, _vp, _sz, _f, _f, _vp]),
     "nd_cw_model_space": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _vp]),
     "nd_cw_control": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

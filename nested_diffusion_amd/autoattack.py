@@ -44,6 +44,29 @@ point in any batch, subset or rank -- where the reference draws from torch.rand 
 
 The checkpoint schedule is fixed, so the host computes it once; every decision runs on the GPU and an iteration of a restart reads
 nothing back to the host (three launches after the input gradient: control, update with the next step fused in).
+
+APGDAttack(norm='L2') is autoattack's APGD-CE in the L2 threat model (AutoAttack(norm='L2')'s first attack), restated from the same
+autopgd_base.py; it is reached through APGDAttack directly, which stands on its own like square.SquareAttack (attack_type 'APGD',
+epsilon, generate_attack) -- the AutoAttack wrapper stays Linf.  Everything of attack_single_run above is shared (input_grad, the
+bookkeeping of nd_apgd_control with step = 2 eps, the checkpoint schedule, x_best / grad_best / x_best_adv, the restore); only the start
+and the step differ.  With n(v) = sqrt(sum v^2) per image (the deterministic row reduction of csrc/nd_attack_l2.hip):
+
+        t = N(0, 1);  x_adv = clamp(x + eps * t / (n(t) + 1e-12), 0, 1)
+        for i < n_iter:
+            grad2 = x_adv - x_adv_old;  x_adv_old = x_adv;  a = 1 if i == 0 else 0.75
+            u  = x_adv + step * grad / (n(grad) + 1e-12)
+            z  = clamp(x + (u - x) / (n(u - x) + 1e-12) * min(eps, n(u - x)), 0, 1)
+            v  = x_adv + (z - x_adv) a + grad2 (1 - a)
+            x_adv = clamp(x + (v - x) / (n(v - x) + 1e-12) * min(eps, n(v - x)), 0, 1)
+
+(nd_apgd_l2_random_start, nd_apgd_l2_step; the flags' copies and the restore run before the step, in nd_apgd_update without a step:
+six launches after the input gradient).  Deviations, documented: a row whose gradient norm is NaN or infinite takes no gradient step
+(u = x_adv), the convention of nd_l2_step; the normals come from the library's Philox and its Box-Muller, keyed as the Linf start is.
+Parity is unpinned, as for Linf.
+
+Expectation over transformation (autoattack's eot_iter, AutoAttack version='rand') is not an argument here: eot.EOTTarget wraps the
+model instead and composes with every gradient attack.  On this project's two-class datasets DLR and the targeted attacks are
+undefined, so APGD-CE on an EOTTarget is what version='rand' reduces to.
 """
 from __future__ import annotations
 
@@ -73,17 +96,22 @@ def apgd_schedule(n_iter: int, n_iter_2: int, n_iter_min: int, size_decr: int) -
 
 
 class APGDAttack:
-    """autoattack's APGDAttack (autopgd_base.py), Linf and the cross-entropy loss: perturb(x, y) -> the adversarial batch.
-    `index` (perturb / attack_single_run): the global image index of each row, which keys its random start."""
+    """autoattack's APGDAttack (autopgd_base.py), norm 'Linf' or 'L2' and the cross-entropy loss: perturb(x, y) -> the adversarial
+    batch, and the surface of the other attacks here (attack_type, epsilon, generate_attack) so that attack.apply_attack,
+    Diffusion.test_atk(attack=...) and make_attacks.write_attacked_set take it.  `index` (perturb / attack_single_run): the global image
+    index of each row, which keys its random start."""
+
+    attack_type = "APGD"
 
     def __init__(self, predict, n_iter=100, norm="Linf", n_restarts=1, eps=None, seed=0, loss="ce", eot_iter=1, rho=.75, topk=None,
                  verbose=False, device=None, use_largereps=False, is_tf_model=False):
-        if norm != "Linf":
-            raise NotImplementedError(f"APGD norm '{norm}' is not implemented (only Linf)")
+        if norm not in ("Linf", "L2"):
+            raise NotImplementedError(f"APGD norm '{norm}' is not implemented (only Linf and L2)")
         if loss != "ce":
             raise NotImplementedError(f"APGD loss '{loss}' is not implemented (only 'ce': apgd-ce)")
         if eot_iter != 1 or use_largereps or is_tf_model:
-            raise NotImplementedError("APGD with eot_iter != 1, use_largereps or a TF model is not implemented")
+            raise NotImplementedError("APGD with eot_iter != 1, use_largereps or a TF model is not implemented (for an expectation over "
+                                      "transformation wrap the model in eot.EOTTarget)")
         if eps is None:
             raise ValueError("eps is required")
         self.model = _vit(predict)
@@ -100,7 +128,10 @@ class APGDAttack:
                           trace: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """(acc, x_best_adv) of one run from a random start.  trace(i, logits, grad, loss, arrays, state), if given, is called after
         the start (i = -1) and after each iteration's update; arrays = dict of x_adv, x_adv_old, x_best, grad_best, x_best_adv (x_adv
-        already holds the next iterate, except after the last iteration) and state = the ops.ApgdState."""
+        already holds the next iterate, except after the last iteration) and state = the ops.ApgdState.  With norm='L2' arrays also
+        carries norms [3, B], the per-image norms of the step just taken (nd_apgd_l2_step)."""
+        if self.norm == "L2":
+            return self._single_run_l2(x, y, index, restart, trace)
         vit, eps = self.model, self.eps
         B = x.shape[0]
         x_adv = ops.apgd_random_start(x, index, eps, self.seed, restart)
@@ -119,6 +150,44 @@ class APGDAttack:
             if trace is not None:
                 trace(i, logits, grad, loss, arrays, st)
         return st.acc.bool(), x_best_adv
+
+    def _single_run_l2(self, x, y, index, restart, trace):
+        """attack_single_run with the L2 start and step: the update without a step makes the flags' copies and the restore, then
+        nd_apgd_l2_step moves x_adv."""
+        vit, eps = self.model, self.eps
+        B = x.shape[0]
+        x_adv = ops.apgd_l2_random_start(x, index, eps, self.seed, restart)
+        logits, grad, loss = vit.input_grad(x_adv, y)
+        st = ops.ApgdState(B, self.n_iter, x.device)
+        ops.apgd_control(logits, y, loss, st, -1, 0, self.thr_decr, step0=2.0 * eps)
+        x_best, x_best_adv, grad_best, x_adv_old = x_adv.clone(), x_adv.clone(), grad.clone(), x_adv.clone()
+        arrays = dict(x_adv=x_adv, x_adv_old=x_adv_old, x_best=x_best, grad_best=grad_best, x_best_adv=x_best_adv)
+        if trace is not None:
+            trace(-1, logits, grad, loss, arrays, st)
+        arrays["norms"] = ops.apgd_l2_step(x, x_adv, x_adv_old, grad, None, None, st.step, eps, 1.0)    # the first step: a = 1
+        for i in range(self.n_iter):
+            logits, grad, loss = vit.input_grad(x_adv, y)
+            flags = ops.apgd_control(logits, y, loss, st, i, self.schedule.get(i, 0), self.thr_decr)
+            ops.apgd_update(None, x_adv, None, grad, x_best, grad_best, x_best_adv, flags, None, eps, 0.75, False)
+            if i + 1 < self.n_iter:
+                arrays["norms"] = ops.apgd_l2_step(x, x_adv, x_adv_old, grad, grad_best, flags, st.step, eps, 0.75)
+            if trace is not None:
+                trace(i, logits, grad, loss, arrays, st)
+        return st.acc.bool(), x_best_adv
+
+    @property
+    def epsilon(self) -> float:
+        """eps under the name the other attacks (and write_attacked_set) use."""
+        return self.eps
+
+    def generate_attack(self, samples: torch.Tensor, labels: torch.Tensor, first_image: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(adversarial images, success), as the other attacks: rows the clean model misclassifies and rows no restart fools come back
+        unchanged; first_image is the global index of samples[0]."""
+        dev = self.model.device
+        labels = labels.to(dev, torch.int64).contiguous()
+        adv = self.perturb(samples, labels, index=first_image + torch.arange(samples.shape[0], dtype=torch.int64))
+        success = self.model.forward(adv).argmax(dim=1) != labels if adv.shape[0] else torch.zeros(0, dtype=torch.bool, device=adv.device)
+        return adv, success
 
     def perturb(self, x: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
         dev = self.model.device

@@ -26,23 +26,6 @@ namespace {
 
 constexpr int L2_THREADS = ND_ATTACK_THREADS;
 
-// the sum over the workgroup, the same bits in every thread (an xor butterfly adds the same two numbers in both partners)
-__device__ __forceinline__ float l2_block_sum(float s, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    __syncthreads();                                     // sh may still be read from a previous sum
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// the finishing pass: partials [parts] of one image (parts <= 256), folded by the same tree
-__device__ __forceinline__ float l2_finish(const float* __restrict__ part, int parts, float* sh) {
-    return l2_block_sum((int)threadIdx.x < parts ? part[threadIdx.x] : 0.f, sh);
-}
-
-__device__ __forceinline__ float l2_sq4(float4 a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
-
 __global__ __launch_bounds__(L2_THREADS) void k_l2_sq_partial(const float* __restrict__ g, float* __restrict__ part, int quads) {
     __shared__ float sh[4];
     const int b = blockIdx.y;

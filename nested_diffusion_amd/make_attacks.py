@@ -1,8 +1,8 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
-    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD --eps E --out ROOT \
+    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD|APGDL2 --eps E --out ROOT \
         [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner|ensemble] [--members 0,1,...] [--mc N] \
-        [--sample_steps N [--skip_type uniform|quadratic] [--eta E]]
+        [--sample_steps N [--skip_type uniform|quadratic] [--eta E]] [--eot N]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
 test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
@@ -20,6 +20,10 @@ test_atk reports, differentiated through the aggregation, the reverse diffusions
 and both paths from the pixels; every gradient step draws fresh sampler noise.  --sample_steps N [--skip_type uniform|quadratic] [--eta E]
 attacks the ensemble as `main --test --sample_steps N` runs it: N of the schedule's timesteps per chain (a sampler plan,
 diffusion_utils.sampler_plan), in time and in tape.
+APGDL2 is autoattack's APGD-CE in the L2 threat model: autoattack.APGDAttack(target, norm='L2', eps, n_restarts=5, n_iter=100, seed); its tree is
+Test_attacks_APGDL2 (no dataset name reads it back, as for SQUARE).  --eot N wraps the chosen target in an eot.EOTTarget for any attack name:
+every gradient of the attack becomes the mean of N gradients at the same point (the accepted way to attack a randomized defence).  An
+EOT-N APGD run on --target ensemble is N x n_iter x n_restarts ensemble gradients: use --sample_steps to keep that affordable.
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ import torch
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="write an attacked test set (Test_attacks_<NAME>) with the GPU attacks of attack.py")
     p.add_argument("--config", type=str, required=True)
-    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "BIM", "L2PGD", "AUTOPGD"], required=True)
+    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "BIM", "L2PGD", "AUTOPGD", "APGDL2"], required=True)
     p.add_argument("--eps", type=float, required=True)
     p.add_argument("--out", type=str, required=True, help="root the Test_attacks_<NAME> tree is written under")
     p.add_argument("--preprocess", type=str, choices=["grayscaled", "standardized"], default="grayscaled")
@@ -51,7 +55,30 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--target ensemble: reverse steps per chain (a sampler plan over the schedule; default: every timestep)")
     p.add_argument("--skip_type", type=str, default=argparse.SUPPRESS, help="with --sample_steps: uniform (default) or quadratic")
     p.add_argument("--eta", type=float, default=argparse.SUPPRESS, help="with --sample_steps: 0 (deterministic) .. 1 (default, ancestral)")
+    p.add_argument("--eot", type=int, default=argparse.SUPPRESS,
+                   help="expectation over transformation: every gradient is the mean of N gradients of the target at the same point")
     return p
+
+
+def eot_wrap(args, target):
+    """The target itself without --eot, else an eot.EOTTarget of it."""
+    if not hasattr(args, "eot"):
+        return target
+    from .eot import EOTTarget
+
+    return EOTTarget(target, args.eot)
+
+
+def make_named_attack(args, target):
+    """The attack --attack_name names, on `target`."""
+    from .attack import make_attack
+    from .autoattack import APGDAttack, AutoAttack
+
+    if args.attack_name == "AUTOPGD":
+        return AutoAttack(target, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
+    if args.attack_name == "APGDL2":
+        return APGDAttack(target, norm="L2", eps=args.eps, n_restarts=5, n_iter=100, seed=args.seed)
+    return make_attack(args.eps, args.attack_name, target, seed=args.seed)
 
 
 def sampler_args(args) -> dict:
@@ -117,8 +144,8 @@ def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
                        device=None) -> int:
-    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner, a SquareAttack or an AutoAttack, which
-    holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
+    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner, a SquareAttack, an APGDAttack or an
+    AutoAttack, which holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
     import types
 
     from PIL import Image
@@ -158,14 +185,14 @@ def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "g
 
 def main(argv=None) -> int:
     from . import main as nd_main
-    from .attack import make_attack
-    from .autoattack import AutoAttack
 
     args = build_parser().parse_args(argv)
     if args.target == "vit" and args.members is not None:
         raise SystemExit("--members selects members of --target conditioner or ensemble")
     if args.target != "ensemble" and hasattr(args, "mc"):
         raise SystemExit("--mc sets the trials of --target ensemble")
+    if hasattr(args, "eot") and args.eot < 1:
+        raise SystemExit(f"--eot must be at least 1 (got {args.eot})")
     sampler = sampler_args(args)
     with open(args.config) as f:
         import yaml
@@ -175,10 +202,7 @@ def main(argv=None) -> int:
         vit = load_ensemble_target(config, device, parse_members(args.members), getattr(args, "mc", 1), args.seed, **sampler)
     else:
         vit = load_vit(config, device) if args.target == "vit" else load_target(config, device, parse_members(args.members))
-    if args.attack_name == "AUTOPGD":
-        attack = AutoAttack(vit, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
-    else:
-        attack = make_attack(args.eps, args.attack_name, vit, seed=args.seed)
+    attack = make_named_attack(args, eot_wrap(args, vit))
     write_attacked_set(config, attack, args.attack_name, args.out, args.preprocess, args.batch_size, args.dataroot, device)
     return 0
 

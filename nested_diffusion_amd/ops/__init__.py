@@ -5,6 +5,7 @@ One module per job, following the csrc/ units and the sections of include/nested
 binds.  Callers reach every wrapper as ops.name: this file only gathers the names."""
 from .._lib import ND_ACT_GELU, ND_ACT_NONE, ND_ACT_RELU, ND_ACT_SOFTPLUS
 from ._base import ACT, _f32, _stream, _workspace, _ws_cache
+from .apgd_l2 import apgd_l2_random_start, apgd_l2_step, eot_add
 from .attack_l2 import (L2_MAX_PARTS, CwState, cw_attack_space, cw_b_half, cw_control, cw_model_space, cw_update, l2_random_start, l2_step,
                         margin_head_grad)
 from .attack_linf import (APGD_IMPROVED, APGD_NOT_PRED, APGD_RESTORE, ApgdState, apgd_control, apgd_random_start, apgd_update,

@@ -1,8 +1,8 @@
-// check_attack_args.hip -- the refusals of the attack entry points (nd_attack_linf.hip, nd_attack_l2.hip, nd_square.hip) as a stand-alone
+// check_attack_args.hip -- the refusals of the attack entry points (nd_attack_linf.hip, nd_attack_l2.hip, nd_apgd_l2.hip, nd_square.hip) as a stand-alone
 // host program: every call below returns ND_ERR_ARG before any HIP call, so it needs no GPU.  Meant for a host-side sanitizer build
 // (CPU only, never on a GPU box); the device pass is left alone:
 //   cd nested_diffusion_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-gpu-sanitize \
-//       ../../tools/check_attack_args.hip nd_error.hip nd_attack_linf.hip nd_attack_l2.hip nd_square.hip -o ../../tools/bin/check_attack_args
+//       ../../tools/check_attack_args.hip nd_error.hip nd_attack_linf.hip nd_attack_l2.hip nd_apgd_l2.hip nd_square.hip -o ../../tools/bin/check_attack_args
 //   ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1 ../../tools/bin/check_attack_args
 #include <stdio.h>
 #include <string.h>
@@ -65,6 +65,21 @@ int main() {
     expect(nd_cw_control(P, I, P, P, P, P, P, J, J, P, 65536, 2, 0, nullptr), "1 <= B <= 65535", "cw_control B=65536");
     expect(nd_cw_update(P, P, P, P, P, P, P, P, J, 0, 8, .01f, .1f, .001f, .5f, nullptr), "cw update needs 1 <= B", "cw_update B=0");
     expect(nd_cw_update(P, P, P, P, P, P, P, Q, J, 2, 8, .01f, .1f, .001f, .5f, nullptr), "cw update needs 16-byte aligned", "cw_update misaligned best");
+
+    expect(nd_apgd_l2_random_start(P, I, nullptr, P, P, 2, 8, 1, 0, .5f, 0, 1, nullptr), "nd_apgd_l2_random_start: NULL", "apgd_l2_start NULL out");
+    expect(nd_apgd_l2_random_start(P, I, P, P, P, 0, 8, 1, 0, .5f, 0, 1, nullptr), "nd_apgd_l2_random_start needs 1 <= B <= 65535", "apgd_l2_start B=0");
+    expect(nd_apgd_l2_random_start(P, I, P, P, P, 2, 6, 1, 0, .5f, 0, 1, nullptr), "per_image % 4 == 0 (B=2, per_image=6)", "apgd_l2_start per_image=6");
+    expect(nd_apgd_l2_random_start(P, I, P, P, P, 2, q31, 1, 0, .5f, 0, 1, nullptr), "nd_apgd_l2_random_start needs 1 <= B", "apgd_l2_start quads=2^31-1");
+    expect(nd_apgd_l2_random_start(P, I, Q, P, P, 2, 8, 1, 0, .5f, 0, 1, nullptr), "nd_apgd_l2_random_start needs 16-byte aligned", "apgd_l2_start misaligned out");
+    expect(nd_apgd_l2_step(nullptr, P, P, P, nullptr, nullptr, P, P, P, 2, 8, .5f, 1.f, nullptr), "nd_apgd_l2_step: NULL", "apgd_l2_step NULL x");
+    expect(nd_apgd_l2_step(P, P, P, P, nullptr, J, P, P, P, 2, 8, .5f, .75f, nullptr), "with flags needs grad_best", "apgd_l2_step flags, no grad_best");
+    expect(nd_apgd_l2_step(P, P, P, P, P, J, P, P, P, 65536, 8, .5f, .75f, nullptr), "nd_apgd_l2_step needs 1 <= B <= 65535", "apgd_l2_step B=65536");
+    expect(nd_apgd_l2_step(P, P, P, P, P, J, P, P, P, 2, 10, .5f, .75f, nullptr), "per_image % 4 == 0 (B=2, per_image=10)", "apgd_l2_step per_image=10");
+    expect(nd_apgd_l2_step(P, P, P, P, Q, J, P, P, P, 2, 8, .5f, .75f, nullptr), "nd_apgd_l2_step needs 16-byte aligned", "apgd_l2_step misaligned grad_best");
+    expect(nd_eot_add(nullptr, P, 8, 0, nullptr), "nd_eot_add: NULL", "eot_add NULL acc");
+    expect(nd_eot_add(P, P, 6, 0, nullptr), "n % 4 == 0", "eot_add n=6");
+    expect(nd_eot_add(P, P, 8, -1, nullptr), "divisor >= 0", "eot_add divisor=-1");
+    expect(nd_eot_add(P, Q, 8, 2, nullptr), "nd_eot_add needs 16-byte aligned", "eot_add misaligned g");
 
     expect(nd_square_init(P, nullptr, P, P, 2, 3, 8, 8, 1, 0, .1f, 0, 1, nullptr), "NULL tensor", "square_init NULL");
     expect(nd_square_init(P, I, P, P, 65536, 3, 8, 8, 1, 0, .1f, 0, 1, nullptr), "(B=65536)", "square_init B=65536");
