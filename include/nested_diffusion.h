@@ -567,6 +567,66 @@ int nd_square_accept(const float *scores_dev, const int64_t *labels_dev, float *
 int nd_square_commit(float *x_best_dev, float *x_new_dev, const int32_t *win_dev, const int32_t *flags_dev, int B, int Cin, int H, int W, int s,
                      void *stream);
 
+/* ---- the Square attack, L2 (the L2 branch of autoattack's square.py; the listing: nested_diffusion_amd/square.py); csrc/nd_square_l2.hip.
+ * B images [B, Cin, H, W] fp32, contiguous (1 <= B <= 65535, 1 <= Cin <= 32, 5 <= H, W <= 4096).  Unlike the Linf form a query rewrites the
+ * whole perturbation: it moves norm budget from window w2 to window w1 (both of odd side s, 3 <= s <= min(H, W)) and renormalises the image
+ * to the eps-sphere, so it needs per-image sums over masked regions and a whole-image write.  Every elementwise value is one rounded fp32
+ * op in the listed order (contraction off); given the sums a call reports, a float32 restatement on the host reproduces every array bit
+ * for bit.  Sums are fp32, without floating-point atomics, in an order fixed by (Cin, H, W, s, the windows): a wave owns one row (c, h) at
+ * a time, a lane the quads w = 4k .. 4k + 3 of it with k = lane, lane + 64, ..., their terms added in ascending w; a workgroup folds its
+ * 256 threads and writes one partial, and the next launch folds the <= ND_L2_MAX_PARTS partials of the image with the same tree.  Neither B,
+ * the row's position in the batch nor the alignment of the arrays changes a bit: where W % 4 == 0 and the arrays are 16-byte aligned a
+ * quad is one 16-byte access, otherwise four scalar ones (W = 30, 5 x 5 images and odd addresses work), with the same terms in the same
+ * order.  Every argument error (ND_ERR_ARG) is found before any HIP call.  No entry point allocates, copies synchronously or
+ * synchronises; one entry point enqueues several kernels on `stream`, and a query stays capturable.  Draws are Philox4x32-10 with key =
+ * (seed low word, seed high word), keyed on index: int64 [B], the GLOBAL image index of each row (its low word).  A row is ACTIVE while
+ * margin_min[b] > 0; any other value (<= 0, -0.0, NaN) freezes it.  ws: B * nd_square_l2_ws_floats(Cin, H, W) floats (the partials;
+ * written before they are read).  eta(s): float [s, s], the unit-norm pattern of the listing, built by the host in float64 and rounded
+ * once; eta_t is eta or, where the transpose bit is set, its transpose.
+ *   nd_square_l2_ws_floats  floats of workspace per image (0 where Cin, H or W is out of range).
+ *   nd_square_l2_init       s0 = min(H, W) / 5, nh = H / s0, nw = W / s0, oh = (H - nh * s0) / 2, ow = (W - nw * s0) / 2.  Tile t = th * nw + tw
+ *                           covers rows oh + th * s0 .. and columns ow + tw * s0 ..; q = philox(counter = (index[b], t, restart,
+ *                           ND_SQUARE_L2_INIT_TAG)); sigma_c = +1 if bit c of q0 is set, else -1; the tile holds eta(s0) transposed if the
+ *                           top bit of q1 is set.  D0 = sigma_c * eta_t(s0) on the tiles, 0 on the margins; sums[b] = sum D0^2;
+ *                           x_best = x_new = clip(x0 + D0 / (1e-12 + sqrt(sums[b])) * eps, lo, hi).  Two launches.
+ *   nd_square_l2_propose    per active row (a frozen row is not touched at all: neither its image, its win nor its sums), with
+ *                           D = x_best - x0: p = philox(counter = (index[b], iter, restart, ND_SQUARE_L2_STEP_TAG)); vh1 = (uint64(p0) *
+ *                           (H - s + 1)) >> 32, vw1 = (uint64(p1) * (W - s + 1)) >> 32, vh2 and vw2 likewise from p2 and p3;
+ *                           q = philox(counter = (index[b], iter, restart, ND_SQUARE_L2_SIGN_TAG)); sigma_c = +1 if bit c of q0 is set,
+ *                           else -1; transpose = the top bit of q1.  win[b] = (vh1, vw1, vh2, vw2), int32 [B, 4].  Then
+ *                               S_w1 = sum_{w1} D^2, S_all = sum D^2, S_mask = sum_{w1 u w2} D^2, S_out = sum_{outside w1 u w2} D^2
+ *                               u = sigma_c * eta_t(s)[dh, dw] + D[w1] / (1e-12 + sqrt(S_w1));  S_u = sum_{w1} u^2
+ *                               scale = sqrt(max(eps * eps - sqrt(S_all) * sqrt(S_all), 0) / Cin + sqrt(S_mask) * sqrt(S_mask))
+ *                               D' = D;  D'[w2] = 0;  D'[w1] = u / (1e-12 + sqrt(S_u)) * scale   (w1 wins where the windows overlap)
+ *                               S_new = sum_{w1} D'^2;  x_new = clip(x0 + D' / (1e-12 + sqrt(S_out + S_new)) * eps, lo, hi)
+ *                           over the whole image.  sums [ND_SQUARE_L2_SUMS, B] receives (S_w1, S_all, S_mask, S_out, S_u, S_new) at rows
+ *                           ND_SQUARE_L2_S_*: exactly the values the elementwise passes used.  Four launches: the masked sums, the two
+ *                           window passes, the write; u and D' are recomputed where they are needed (the same bits), never stored.
+ *                           x_new must be neither x0 nor x_best.  iter >= 0.
+ *   nd_square_l2_commit     rows whose flags (nd_square_accept) hold ND_SQUARE_ACTIVE | ND_SQUARE_ACCEPT: x_best = x_new over the whole
+ *                           image of per_image = Cin * H * W elements; every other row: nothing.  A rejected candidate is not taken back:
+ *                           the next propose rewrites the whole of x_new.
+ * The bookkeeping of a query is nd_square_accept, unchanged. */
+#define ND_SQUARE_L2_INIT_TAG 0x53324931u
+#define ND_SQUARE_L2_STEP_TAG 0x53325331u
+#define ND_SQUARE_L2_SIGN_TAG 0x53324731u
+#define ND_SQUARE_L2_SUMS 6
+#define ND_SQUARE_L2_S_W1 0
+#define ND_SQUARE_L2_S_ALL 1
+#define ND_SQUARE_L2_S_MASK 2
+#define ND_SQUARE_L2_S_OUT 3
+#define ND_SQUARE_L2_S_U 4
+#define ND_SQUARE_L2_S_NEW 5
+size_t nd_square_l2_ws_floats(int Cin, int H, int W);
+int nd_square_l2_init(const float *x0_dev, const int64_t *index_dev, const float *eta0_dev, float *x_best_dev, float *x_new_dev,
+                      float *sums_dev, float *ws_dev, int B, int Cin, int H, int W, int s0, uint64_t seed, uint32_t restart, float eps,
+                      float lo, float hi, void *stream);
+int nd_square_l2_propose(const float *x0_dev, const float *x_best_dev, float *x_new_dev, const int64_t *index_dev,
+                         const float *margin_min_dev, const float *eta_dev, int32_t *win_dev, float *sums_dev, float *ws_dev, int B,
+                         int Cin, int H, int W, int s, int iter, uint64_t seed, uint32_t restart, float eps, float lo, float hi,
+                         void *stream);
+int nd_square_l2_commit(float *x_best_dev, const float *x_new_dev, const int32_t *flags_dev, int B, size_t per_image, void *stream);
+
 /* ---- the L2 attacks (foolbox 3.x L2BasicIterativeAttack / L2ProjectedGradientDescentAttack) and Carlini & Wagner's L2 attack
  * (L2CarliniWagnerAttack); the listings: nested_diffusion_amd/attack.py.  B images of per_image fp32 elements (per_image % 4 == 0,
  * 1 <= B <= 65535, images 16-byte aligned); every elementwise operation one rounded fp32 op in the listing's order (contraction off).

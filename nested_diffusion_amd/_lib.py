@@ -192,6 +192,10 @@ SIGNATURES = {
     "nd_square_propose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
     "nd_square_accept": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "nd_square_commit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "nd_square_l2_ws_floats": (_sz, [_i, _i, _i]),
+    "nd_square_l2_init": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_square_l2_propose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint32, _f, _f, _f, _vp]),
+    "nd_square_l2_commit": (_i, [_vp, _vp, _vp, _i, _sz, _vp]),
     "nd_l2_parts": (_i, [_sz]),
     "nd_margin_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "nd_l2_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _f, _f, _f, _f, _vp]),

@@ -263,8 +263,8 @@ def make_attack(epsilon: float, attack_type: str, model, seed: int = 0):
 def apply_attack(attack_func, images_in: torch.Tensor, labels_in: torch.Tensor, attack_name: str,
                  first_image: int = 0) -> torch.Tensor:
     """utils.py:258-269: the adversarial images of a batch (the inputs are not modified).  attack_func is anything with
-    generate_attack(samples, labels, first_image=) -- an Attack, an L2Attack, a CarliniWagner, a square.SquareAttack or an
-    autoattack.APGDAttack; AUTOPGD takes an autoattack.AutoAttack
+    generate_attack(samples, labels, first_image=) -- an Attack, an L2Attack, a CarliniWagner, a square.SquareAttack or SquareL2Attack, an
+    autoattack.APGDAttack or an autoattack.WorstCase; AUTOPGD takes an autoattack.AutoAttack
     (run_standard_evaluation with bs = the batch, as utils.py:263-266 calls it)."""
     if attack_name == "AUTOPGD":
         from .autoattack import AutoAttack

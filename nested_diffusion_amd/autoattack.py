@@ -259,3 +259,68 @@ class AutoAttack:
                 robust[b[false]] = False
                 x_adv[b[false]] = adv_curr[false]
         return x_adv
+
+
+class WorstCase:
+    """AutoAttack's evaluation order for any list of attacks that have perturb(x, y, index=), norm and eps: the per-image worst case.
+    Rows the clean model gets wrong come back unchanged; each attack, in the order given, sees only the rows still robust, with their
+    global indices; the first adversarial found for a row is kept, and robust_after records (name, robust count) after each attack.
+    On this project's two-class datasets the L2 evaluation is WorstCase(t, [APGDAttack(t, norm='L2', ...), SquareL2Attack(t, ...)]):
+    APGD-T, APGD-DLR and FAB-T are undefined with two classes.  attack_type = "WORSTCASE", epsilon and generate_attack: the surface
+    attack.apply_attack, Diffusion.test_atk(attack=...) and make_attacks.write_attacked_set take."""
+
+    attack_type = "WORSTCASE"
+
+    def __init__(self, model, attacks):
+        attacks = list(attacks)
+        if not attacks:
+            raise ValueError("WorstCase needs at least one attack")
+        for a in attacks:
+            if not callable(getattr(a, "perturb", None)) or not hasattr(a, "norm") or not hasattr(a, "eps"):
+                raise TypeError(f"WorstCase members need perturb(x, y, index=), norm and eps ({self._name(a)} does not)")
+        first = attacks[0]
+        for a in attacks[1:]:
+            if a.norm != first.norm or float(a.eps) != float(first.eps):
+                raise ValueError(f"WorstCase members disagree on the threat model: {self._name(first)} has norm={first.norm!r}, eps={first.eps!r} "
+                                 f"and {self._name(a)} has norm={a.norm!r}, eps={a.eps!r}")
+        self.model = _vit(model)
+        forward = getattr(self.model, "forward", self.model)
+        if not callable(forward):
+            raise TypeError("model must have forward(x) -> [B, C] scores or be such a callable")
+        self.predict = forward
+        self.attacks = attacks
+        self.norm, self.eps = first.norm, float(first.eps)
+        self.epsilon = self.eps
+        self.robust_after: List[Tuple[str, int]] = []
+
+    @staticmethod
+    def _name(a) -> str:
+        return str(getattr(a, "attack_type", type(a).__name__))
+
+    def perturb(self, x: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The adversarial batch; fills robust_after with ("clean", n) and one entry per attack that ran."""
+        dev = getattr(self.model, "device", None) or x.device
+        x = x.to(dev, torch.float32).contiguous()
+        y = y.to(dev, torch.int64).contiguous()
+        index = (torch.arange(x.shape[0]) if index is None else index).to(dev, torch.int64)
+        adv = x.clone()
+        robust = self.predict(x).argmax(dim=1) == y if x.shape[0] else torch.zeros(0, dtype=torch.bool, device=dev)
+        self.robust_after = [("clean", int(robust.sum()))]
+        for a in self.attacks:
+            ids = robust.nonzero().flatten()
+            if ids.numel() == 0:
+                break
+            xb, yb = x[ids].contiguous(), y[ids].contiguous()
+            adv_curr = a.perturb(xb, yb, index=index[ids].contiguous()).to(dev)
+            fooled = self.predict(adv_curr).argmax(dim=1) != yb
+            robust[ids[fooled]] = False
+            adv[ids[fooled]] = adv_curr[fooled]
+            self.robust_after.append((self._name(a), int(robust.sum())))
+        return adv
+
+    def generate_attack(self, samples: torch.Tensor, labels: torch.Tensor, first_image: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(adversarial images, success), as the other attacks; first_image is the global index of samples[0]."""
+        adv = self.perturb(samples, labels, index=first_image + torch.arange(samples.shape[0], dtype=torch.int64))
+        labels = labels.to(adv.device, torch.int64)
+        success = self.predict(adv).argmax(dim=1) != labels if adv.shape[0] else torch.zeros(0, dtype=torch.bool, device=adv.device)
+        return adv, success

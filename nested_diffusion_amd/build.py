@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnd_hip.so")
 SOURCES = ["nd_skinny_m0.hip", "nd_skinny_m1.hip", "nd_skinny_m2.hip", "nd_pack.hip", "nd_error.hip", "nd_step.hip", "nd_handle.hip", "nd_sampler.hip", "nd_linear.hip", "nd_report.hip", "nd_gemm_nt.hip", "nd_layernorm.hip", "nd_attention_h.hip", "nd_patchify.hip", "nd_image.hip", "nd_cond_gemm.hip", "nd_attention.hip", "nd_attention_b9.hip", "nd_gemm_f32.hip",
-           "nd_conditioner.hip", "nd_rng.hip", "nd_gemm_b9.hip", "nd_persist.hip", "nd_vit_grad.hip", "nd_attack_linf.hip", "nd_attack_l2.hip", "nd_apgd_l2.hip", "nd_square.hip", "nd_mlp_grad.hip", "nd_mlp_train.hip", "nd_vit_train.hip", "nd_diffusion_train.hip", "nd_ensemble_grad.hip"]
+           "nd_conditioner.hip", "nd_rng.hip", "nd_gemm_b9.hip", "nd_persist.hip", "nd_vit_grad.hip", "nd_attack_linf.hip", "nd_attack_l2.hip", "nd_apgd_l2.hip", "nd_square.hip", "nd_square_l2.hip", "nd_mlp_grad.hip", "nd_mlp_train.hip", "nd_vit_train.hip", "nd_diffusion_train.hip", "nd_ensemble_grad.hip"]
 # per-file flags: the large-M tile kernel keeps its accumulators in VGPRs (see nd_cond_gemm.hpp)
 EXTRA_FLAGS = {"nd_cond_gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "nd_attention_b9.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_gemm_f32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "nd_gemm_b9.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}

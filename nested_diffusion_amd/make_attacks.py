@@ -1,8 +1,8 @@
 """Writes the attacked test sets the reference evaluates (its ChestXRayAtk* / ISICSkinCancerAtk* datasets), on the GPU:
 
-    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD|APGDL2 --eps E --out ROOT \
+    python -m nested_diffusion_amd.make_attacks --config <yml> --attack_name FGSM|PGD|BIM|L2PGD|AUTOPGD|APGDL2|SQUARE|SQUAREL2 --eps E --out ROOT \
         [--preprocess grayscaled] [--seed S] [--batch_size B] [--target vit|conditioner|ensemble] [--members 0,1,...] [--mc N] \
-        [--sample_steps N [--skip_type uniform|quadratic] [--eta E]] [--eot N]
+        [--sample_steps N [--skip_type uniform|quadratic] [--eta E]] [--eot N] [--n_queries N]
 
 Loads the ViT checkpoint the runner would load (<trained_aux_cls_ckpt_path>/vit_base_patch16_224_<Dataset>.pth), attacks the config's
 test split (the PGD / APGD random start of an image is keyed on its index in the dataset) and writes ROOT/Test_attacks_<NAME>/<class>/<stem>.png
@@ -24,6 +24,9 @@ APGDL2 is autoattack's APGD-CE in the L2 threat model: autoattack.APGDAttack(tar
 Test_attacks_APGDL2 (no dataset name reads it back, as for SQUARE).  --eot N wraps the chosen target in an eot.EOTTarget for any attack name:
 every gradient of the attack becomes the mean of N gradients at the same point (the accepted way to attack a randomized defence).  An
 EOT-N APGD run on --target ensemble is N x n_iter x n_restarts ensemble gradients: use --sample_steps to keep that affordable.
+SQUARE and SQUAREL2 are the score-based attacks square.SquareAttack (Linf) and square.SquareL2Attack (L2) on the chosen target, the control for
+gradient masking; --n_queries N (default 5000) is their query budget and is refused with any other attack name.  Their trees are
+Test_attacks_SQUARE and Test_attacks_SQUAREL2 (no dataset name reads them back).
 """
 from __future__ import annotations
 
@@ -38,7 +41,7 @@ import torch
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="write an attacked test set (Test_attacks_<NAME>) with the GPU attacks of attack.py")
     p.add_argument("--config", type=str, required=True)
-    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "BIM", "L2PGD", "AUTOPGD", "APGDL2"], required=True)
+    p.add_argument("--attack_name", type=str, choices=["FGSM", "PGD", "BIM", "L2PGD", "AUTOPGD", "APGDL2", "SQUARE", "SQUAREL2"], required=True)
     p.add_argument("--eps", type=float, required=True)
     p.add_argument("--out", type=str, required=True, help="root the Test_attacks_<NAME> tree is written under")
     p.add_argument("--preprocess", type=str, choices=["grayscaled", "standardized"], default="grayscaled")
@@ -57,7 +60,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eta", type=float, default=argparse.SUPPRESS, help="with --sample_steps: 0 (deterministic) .. 1 (default, ancestral)")
     p.add_argument("--eot", type=int, default=argparse.SUPPRESS,
                    help="expectation over transformation: every gradient is the mean of N gradients of the target at the same point")
+    p.add_argument("--n_queries", type=int, default=argparse.SUPPRESS, help="SQUARE / SQUAREL2: the query budget (default 5000)")
     return p
+
+
+SQUARE_NAMES = ("SQUARE", "SQUAREL2")
+
+
+def check_n_queries(args) -> None:
+    """--n_queries belongs to the Square attacks: refused by name (SystemExit) with any other attack, and below 1."""
+    if not hasattr(args, "n_queries"):
+        return
+    if args.attack_name not in SQUARE_NAMES:
+        raise SystemExit(f"--n_queries is the query budget of --attack_name SQUARE or SQUAREL2 (got {args.attack_name})")
+    if args.n_queries < 1:
+        raise SystemExit(f"--n_queries must be at least 1 (got {args.n_queries})")
 
 
 def eot_wrap(args, target):
@@ -78,6 +95,11 @@ def make_named_attack(args, target):
         return AutoAttack(target, eps=args.eps, seed=args.seed, version="custom", norm="Linf", attacks_to_run=["apgd-ce"])
     if args.attack_name == "APGDL2":
         return APGDAttack(target, norm="L2", eps=args.eps, n_restarts=5, n_iter=100, seed=args.seed)
+    if args.attack_name in SQUARE_NAMES:
+        from .square import SquareAttack, SquareL2Attack
+
+        cls = SquareAttack if args.attack_name == "SQUARE" else SquareL2Attack
+        return cls(target, eps=args.eps, n_queries=getattr(args, "n_queries", 5000), seed=args.seed)
     return make_attack(args.eps, args.attack_name, target, seed=args.seed)
 
 
@@ -144,8 +166,8 @@ def load_ensemble_target(config, device, members=None, mc: int = 1, seed: int = 
 
 def write_attacked_set(config, attack, name: str, out: str, preprocess: str = "grayscaled", batch_size: int = 32, dataroot: str = None,
                        device=None) -> int:
-    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner, a SquareAttack, an APGDAttack or an
-    AutoAttack, which holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
+    """Attacks the clean test split of the config's dataset with `attack` (an Attack, an L2Attack, a CarliniWagner, a SquareAttack or SquareL2Attack, an APGDAttack, a
+    WorstCase or an AutoAttack, which holds the ViT it attacks) and writes out/Test_attacks_<name>; returns the number of successful attacks."""
     import types
 
     from PIL import Image
@@ -193,6 +215,7 @@ def main(argv=None) -> int:
         raise SystemExit("--mc sets the trials of --target ensemble")
     if hasattr(args, "eot") and args.eot < 1:
         raise SystemExit(f"--eot must be at least 1 (got {args.eot})")
+    check_n_queries(args)
     sampler = sampler_args(args)
     with open(args.config) as f:
         import yaml

@@ -20,6 +20,7 @@ from .optim import (COLSUM_CHUNK, adam_step, adamw_step, bias_grad_adam, colsum_
 from .packed_linear import LINEAR_BWD_MAX_M, PackedWeight, linear, linear_grad_input
 from .report_tail import aggregate, report, sample_stats, softmax_rows
 from .square import SQUARE_ACCEPT, SQUARE_ACTIVE, SquareState, square_accept, square_commit, square_init, square_propose
+from .square_l2 import SQUARE_L2_SUMS, SquareL2State, square_l2_commit, square_l2_init, square_l2_propose, square_l2_ws_floats
 from .vit import (attention, attention_images, attention_split, gemm_split_qkv, layernorm, layernorm_split, patchify, patchify_split,
                   qkv_images_supported)
 from .vit_grad import (ATTENTION_BWD_MAX_TOKENS, attention_grad, gelu_grad_split, gelu_split, layernorm_grad, unpatchify,

@@ -49,12 +49,67 @@ Deviations, documented:
 
 predict is a VisionTransformer, a GuidingConditioner (its ViT, as for the other attacks) or any callable that maps a float32
 [B, Cin, H, W] device tensor to a float32 [B, C] device tensor.
+
+The L2 form (SquareL2Attack; nd_square_l2_init, nd_square_l2_propose, nd_square_accept, nd_square_l2_commit).  It is not the Linf kernels
+with another constant: every query moves norm budget from one window to another and renormalises the whole perturbation to the
+eps-sphere, so it needs per-image sums over masked regions and a whole-image rewrite per query.  Restated from autoattack's square.py,
+L2 branch; this listing governs (all arrays per image; every elementwise operation one rounded fp32 op in this order; sums are fp32 in
+an order fixed by (Cin, H, W, s, the windows), never by B or the row's place in the batch):
+
+    eta_rectangles(a, b): d = zeros[a, b]; xc, yc = a//2 + 1, b//2 + 1; c2 = [xc - 1, yc - 1]
+        for k in range(max(xc, yc)):
+            d[max(c2[0],0):min(c2[0] + 2k + 1, a), max(c2[1],0):min(c2[1] + 2k + 1, b)] += 1/(k + 1)^2
+            c2[0] -= 1; c2[1] -= 1
+        return d / sqrt(sum d^2)
+    eta(s): d = zeros[s, s]; d[:s//2] = eta_rectangles(s//2, s); d[s//2:] = -eta_rectangles(s - s//2, s)
+        return d / sqrt(sum d^2)
+            # host, float64, rounded once to fp32, cached per s, uploaded as [s, s]
+            # eta(3) = [[.13608276, .68041382, .13608276],
+            #           [-.12909944, -.12909944, -.12909944],
+            #           [-.12909944, -.64549722, -.12909944]]
+            # eta(1) = [[-1]]
+    side_l2(it, H, W): s = max(int(round(sqrt(p_selection(it) * H * W))), 3)
+        if s even: s += 1
+        s = min(s, largest odd <= min(H, W))        # the min is this project's clamp
+    init: s0 = min(H, W) // 5; nh, nw = H // s0, W // s0; oh, ow = (H - nh*s0)//2, (W - nw*s0)//2
+        D0 = 0
+        tile (th, tw) of every channel c:  += sigma(b, c, tile) * (eta(s0) or its transpose, per (b, tile))
+        x_best = x_new = clip(x + D0 / (1e-12 + ||D0||) * eps, lo, hi)                                        nd_square_l2_init
+    query i, per ACTIVE row (margin_min > 0), D = x_best - x:                                                 nd_square_l2_propose
+        windows w1 = (vh1, vw1), w2 = (vh2, vw2), both of side s = side_l2(i)
+        sign sigma_c per channel; transpose bit t
+        S_w1  = sum_{w1} D^2
+        S_all = sum D^2
+        S_mask = sum_{w1 u w2} D^2        # an element in both windows counts once
+        S_out = sum_{outside w1 u w2} D^2
+        n_w1 = sqrt(S_w1); n_img = sqrt(S_all); n_mask = sqrt(S_mask)
+        u = sigma_c * eta_t(s)[i, j] + D[w1] / (1e-12 + n_w1);  S_u = sum u^2;  n_u = sqrt(S_u)
+        scale = sqrt(max(eps*eps - n_img*n_img, 0) / Cin + n_mask*n_mask)
+        D' = D;  D'[w2] = 0;  D'[w1] = u / (1e-12 + n_u) * scale        # w1 wins where the windows overlap
+        S_new = sum_{w1} D'^2;  n' = sqrt(S_out + S_new)
+        x_new = clip(x + D' / (1e-12 + n') * eps, lo, hi)
+    accept / bookkeeping: exactly nd_square_accept (loss = margin; improved = loss < loss_min; accept = improved or margin <= 0)
+    commit: accepted rows: x_best = x_new (whole image); nothing else                                         nd_square_l2_commit
+
+perturb, restarts, generate_attack, check_every, trace, the frozen-row convention and p_selection are those of SquareAttack.
+Deviations of the L2 form, documented:
+  - autoattack draws one pair of windows, one sign per channel and one eta orientation for the whole batch; here every image draws its
+    own from Philox keyed on (seed, the image's global index, query or tile, restart).
+  - each sign and each transpose comes from one random bit, where autoattack takes a uniform draw (and, at the start, a random choice).
+  - the tile origin: the start tiles nh x nw whole tiles of side s0 centred in the image (margins of (H - nh*s0)//2 rows and
+    (W - nw*s0)//2 columns stay 0), where autoattack's h//s loop starts at the corner and assumes a side of 5 * s0; side_l2's last min
+    is this project's clamp for images that are not square or smaller than the schedule's window.
+  - rejected rows are not restored: x_new keeps the rejected candidate, and the next propose rewrites the whole image from x_best.
+  - on a target whose forward is random (an EnsembleTarget without fix_noise()) every query is a fresh draw of the defence: the margin
+    a candidate is accepted on is one sample, as it is for autoattack on a randomized model.
+Images below 5 x 5 have no start (s0 = 0) and are refused.
 """
 from __future__ import annotations
 
 import math
-from typing import Callable, Optional, Tuple
+from typing import Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -72,7 +127,7 @@ class SquareAttack:
     def __init__(self, predict, norm="Linf", n_queries=5000, eps=None, p_init=.8, n_restarts=1, seed=0, verbose=False, targeted=False,
                  loss="margin", resc_schedule=True, device=None, check_every=50):
         if norm != "Linf":
-            raise NotImplementedError(f"Square norm '{norm}' is not implemented (only Linf)")
+            raise NotImplementedError(f"Square norm '{norm}' is not implemented here (only Linf; the L2 form is square.SquareL2Attack)")
         if loss != "margin":
             raise NotImplementedError(f"Square loss '{loss}' is not implemented (only 'margin')")
         if targeted:
@@ -171,3 +226,95 @@ class SquareAttack:
         adv = self.perturb(samples, labels, index=index)
         success = self._scores(adv).argmax(dim=1) != labels if adv.shape[0] else torch.zeros(0, dtype=torch.bool, device=adv.device)
         return adv, success
+
+
+def eta_rectangles(a: int, b: int) -> np.ndarray:
+    """The listing's eta_rectangles in float64: nested centred rectangles weighted 1 / (k + 1)^2, unit L2 norm."""
+    d = np.zeros((a, b), dtype=np.float64)
+    xc, yc = a // 2 + 1, b // 2 + 1
+    c2 = [xc - 1, yc - 1]
+    for k in range(max(xc, yc)):
+        d[max(c2[0], 0):min(c2[0] + 2 * k + 1, a), max(c2[1], 0):min(c2[1] + 2 * k + 1, b)] += 1.0 / (k + 1) ** 2
+        c2[0] -= 1
+        c2[1] -= 1
+    return d / np.sqrt((d ** 2).sum())
+
+
+def eta_pattern(s: int) -> np.ndarray:
+    """The listing's eta(s): float32 [s, s] of unit L2 norm, computed in float64 and rounded once."""
+    d = np.zeros((s, s), dtype=np.float64)
+    if s // 2:
+        d[:s // 2] = eta_rectangles(s // 2, s)
+    d[s // 2:] = -eta_rectangles(s - s // 2, s)
+    return (d / np.sqrt((d ** 2).sum())).astype(np.float32)
+
+
+class SquareL2Attack(SquareAttack):
+    """autoattack's SquareAttack with norm='L2' and the margin loss, untargeted, on the nd_square_l2_* kernels: the surface of
+    SquareAttack (perturb, attack_single_run, generate_attack, attack_type, epsilon), the same schedule, restarts and frozen-row
+    convention.  eta(s) is built on the host once per side and kept on the device."""
+
+    attack_type = "SQUAREL2"
+    MIN_DIM = 5
+
+    def __init__(self, predict, n_queries=5000, eps=None, p_init=.8, n_restarts=1, seed=0, verbose=False, resc_schedule=True, device=None,
+                 check_every=50):
+        # the parent checks and stores everything the two forms share; its norm argument names the Linf form only
+        super().__init__(predict, norm="Linf", n_queries=n_queries, eps=eps, p_init=p_init, n_restarts=n_restarts, seed=seed, verbose=verbose,
+                         resc_schedule=resc_schedule, device=device, check_every=check_every)
+        self.norm = "L2"
+        self._eta: Dict[Tuple[int, str], torch.Tensor] = {}
+
+    def side(self, it: int, H: int, W: int) -> int:
+        """side_l2 of the listing: odd, at least 3, at most the largest odd number <= min(H, W)."""
+        s = max(int(round(math.sqrt(self.p_selection(it) * H * W))), 3)
+        s += 1 - s % 2
+        m = min(H, W)
+        return min(s, m - 1 + m % 2)
+
+    def eta(self, s: int, device=None) -> torch.Tensor:
+        """eta(s) as float32 [s, s] on `device` (None: the host), cached per (s, device)."""
+        key = (int(s), str(device))
+        if key not in self._eta:
+            t = torch.from_numpy(eta_pattern(int(s)))
+            self._eta[key] = t if device is None else t.to(device)
+        return self._eta[key]
+
+    @classmethod
+    def check_size(cls, H: int, W: int) -> None:
+        if min(H, W) < cls.MIN_DIM:
+            raise ValueError(f"SquareL2Attack needs images of at least {cls.MIN_DIM} x {cls.MIN_DIM} (got {H} x {W}): the start tiles "
+                             "the image with squares of side min(H, W) // 5")
+
+    def attack_single_run(self, x: torch.Tensor, y: torch.Tensor, index: torch.Tensor, restart: int = 0,
+                          trace: Optional[Callable] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(n_queries, x_best) of one run from the tiled start.  trace(i, scores, arrays, state), if given, is called after the start
+        (i = -1) and after each query's commit; arrays = dict of x_best, x_new and init_sums (sum D0^2 [B]); state = the
+        ops.SquareL2State, whose win and sums are those of the query."""
+        eps, seed = self.eps, self.seed
+        B, Cin, H, W = x.shape
+        self.check_size(H, W)
+        x_best, x_new, init_sums = ops.square_l2_init(x, index, self.eta(min(H, W) // 5, x.device), eps, seed, restart, *BOUNDS)
+        st = ops.SquareL2State(B, Cin, H, W, x.device)
+        scores = self._scores(x_new)
+        ops.square_accept(scores, y, st, -1)
+        arrays = dict(x_best=x_best, x_new=x_new, init_sums=init_sums)
+        if trace is not None:
+            trace(-1, scores, arrays, st)
+        for i in range(self.n_queries):
+            if self.check_every and i % self.check_every == 0 and int((st.margin_min > 0).sum()) == 0:
+                break                                              # the loop's only read-back: no row is active any more
+            s = self.side(i, H, W)
+            ops.square_l2_propose(x, x_best, x_new, index, st, self.eta(s, x.device), s, i, eps, seed, restart, *BOUNDS)
+            scores = self._scores(x_new)
+            ops.square_accept(scores, y, st, i)
+            ops.square_l2_commit(x_best, x_new, st)
+            if trace is not None:
+                trace(i, scores, arrays, st)
+        return st.n_queries, x_best
+
+    def perturb(self, x: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The adversarial batch, as SquareAttack.perturb; images below 5 x 5 are refused before the model is called."""
+        if x.dim() == 4:
+            self.check_size(x.shape[2], x.shape[3])
+        return super().perturb(x, y, index=index)
